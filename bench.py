@@ -11,6 +11,12 @@ loops) + 1000 injected outliers => N=1256, 789,396 cells (i <= j).  Synthetic st
 INTEL file itself is not shipped with the reference and there is no network.
 
 python bench.py --gpus N --steps K --warmup W [--workload C1|C2|C3|C4|C4m|C5|T4k|T700|T2400]
+                [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (`ms_per_step`: one timed step).
+--dump-outputs DIR writes what the last timed step computed (accepted set, consistency matrix, per-cell chi2) as .npy.
+--full adds everything else: roofline, single-shot first step, CPU baseline, the literal trial loop on the GPU, the
+reference's incremental metric and final map, the set-only mode.
 """
 import argparse
 import json
@@ -363,81 +369,41 @@ def executed_flops(workload, dim):
                 mfma_mops_f64=c.get("SQ_INSTS_VALU_MFMA_MOPS_F64"), source=os.path.relpath(path, ROOT), current=current)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--workload", default="C2")
-    ap.add_argument("--cpu-seconds", type=float, default=30.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-set-only", action="store_true", help="skip the set-only side measurement (kernel traces of the matrix steps alone)")
-    ap.add_argument("--incremental-candidates", type=int, default=None,
-                    help="candidates of the faithful incremental mode to time (reference metric); -1: all of them (C4: minutes, "
-                         "C5: tens of minutes -- one run instead of three); 0: none; default: all for C1 / C2 / tiny / T700 at 1 GPU, "
-                         "none otherwise")
-    args = ap.parse_args()
+DUMP_MATRIX_ELEMS = 4 * 1024 * 1024     # --dump-outputs: at most 16 MB of float32 matrix rows ...
+DUMP_CELLS = 1024 * 1024                # ... and 20 MB of per-cell records (i, j float32, max_chi2 float64, iterations float32)
 
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # plain `python bench.py --gpus N`: re-launch as N ranks (one per GPU) under torch.distributed.run
-        import socket
-        with socket.socket() as so:
-            so.bind(("127.0.0.1", 0))
-            port = so.getsockname()[1]
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
-                                  "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
-                                  "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    if world != args.gpus:
-        raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
-    import torch.distributed as dist
-    from ipc_amd.consensus import IPC
-    from ipc_amd.dist import EngineBackend, ShardedMatrix
 
-    torch.cuda.set_device(local_rank)
-    if world > 1:
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        dist.init_process_group("nccl", rank=rank, world_size=world,
-                                device_id=torch.device("cuda", local_rank))
+def dump_outputs(path, bits, acc, cells, N):
+    """What the timed path computed in its last step, as float32 / float64 .npy files under `path` (at most ~36 MB):
+    the accepted set, the symmetric consistency matrix (all rows, or a fixed seeded sample of rows when N x N exceeds
+    DUMP_MATRIX_ELEMS) and the solved cells of this rank sorted by (i, j) (a fixed seeded sample beyond DUMP_CELLS).
+    Every sampled array comes with the indices it was taken at."""
+    from ipc_amd.consensus import unpack_bits
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "accepted.npy"), acc.astype(np.float32))
+    rows = np.arange(N)
+    if N * N > DUMP_MATRIX_ELEMS:
+        rows = np.sort(np.random.default_rng(0).choice(N, DUMP_MATRIX_ELEMS // N, replace=False))
+    np.save(os.path.join(path, "consistency_matrix.npy"), unpack_bits(bits[rows], N).astype(np.float32))
+    np.save(os.path.join(path, "consistency_matrix_rows.npy"), rows.astype(np.float32))
+    cells = cells[np.lexsort((cells["j"], cells["i"]))]
+    if len(cells) > DUMP_CELLS:
+        cells = cells[np.sort(np.random.default_rng(1).choice(len(cells), DUMP_CELLS, replace=False))]
+    np.save(os.path.join(path, "cell_ij.npy"), np.stack([cells["i"], cells["j"]], axis=1).astype(np.float32))
+    np.save(os.path.join(path, "cell_max_chi2.npy"), cells["max_chi2"].astype(np.float64))
+    np.save(os.path.join(path, "cell_iterations.npy"), cells["iterations"].astype(np.float32))
 
-    g, cfg, desc = build_workload(args.workload)
-    eng = IPC(g, cfg, device=local_rank)               # chain + candidates now resident in HBM
-    sm = ShardedMatrix(EngineBackend(eng), rank, world)
-    N = eng.N
-    n_cells_total = N * (N + 1) // 2
 
-    def barrier():
-        if world > 1:
-            dist.barrier()
-        torch.cuda.synchronize()
-
-    for _ in range(args.warmup):
-        sm.step()
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        sm.step()
-    barrier()
-    dt = time.perf_counter() - t0
-    # per-step solver time from HIP events recorded on the launch stream (last step)
-    sms, launches = eng.solver_time_ms()
-    if world > 1:
-        t = torch.tensor([dt], dtype=torch.float64, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t.item())
-    ms_per_step = dt / args.steps * 1e3
-
-    # ---- roofline of the dominant kernel (the cell solver launches of one step) ----
-    cells = eng.cell_info()                            # this rank's solved cells
+def roofline_figures(args, g, cells, sms, launches, world):
+    """Roofline of the dominant kernel (the cell solver launches of one step): FP64 and HBM, from this run's HIP-event
+    kernel time and the committed counter passes under profiles/."""
     L = (cells["hi"] - cells["lo"]).astype(np.float64)
     nl = np.where(cells["i"] == cells["j"], 1, 2)
     bo = B_ODOM if g.dim == 2 else B_ODOM3
     alg_bytes = float((L * bo + nl * bo + 1.0 / 8).sum())
     # HBM traffic of the solver kernels from the committed rocprofv3 PMC passes of this same command
-    # (FETCH_SIZE / WRITE_SIZE in KB, separate passes; FETCH_SIZE doubled per the gfx950 note in
-    # MI355X_MICROARCH.md).  Per step, like `achieved`.
+    # (FETCH_SIZE / WRITE_SIZE in KB, separate passes; FETCH_SIZE doubled per the gfx950 note on
+    # those counters).  Per step, like `achieved`.
     traffic = None
     for rnd in ("r6_", "r5_", "r4_", ""):
         pmc_csv = os.path.join(ROOT, "profiles", "%spmc_hbm_%s.csv" % (rnd, args.workload))
@@ -491,29 +457,17 @@ def main():
     roofline_hbm = {"bound": "hbm", "achieved": round(hbm_gbs, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                     "frac": round(hbm_gbs / HBM_PEAK_GBS, 6), "traffic": traffic,
                     "algorithmic_bytes_per_step": alg_bytes}
+    return roofline, roofline_hbm
 
-    out = {
-        "metric": "candidate-pairs/s (consistency matrix + set-max)",
-        "value": n_cells_total * args.steps / dt,
-        "unit": "candidate-pairs/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {"workload": "%s: %s; N=%d candidates, %d cells (i<=j), %d solved on rank 0, "
-                               "s=%.0f, fast %.3f/%d, slow %.3f/%d" % (
-                                   args.workload, desc, N, n_cells_total, len(cells), cfg.s_factor,
-                                   cfg.fast_reject_th, cfg.fast_reject_iter_base, cfg.slow_reject_th,
-                                   cfg.slow_reject_iter_base),
-                   "parallelism": "rows%%%d + all-gather" % world if world > 1 else "1 GPU"},
-        "roofline": roofline,
-        "roofline_hbm": roofline_hbm,
-    }
-    bits, acc = sm.result()
-    out["accepted"] = int(acc.sum())
+
+def full_measurements(args, out, g, cfg, eng, acc, cells, sms, launches, ms_per_step, rank, local_rank, world, barrier):
+    """--full: everything beyond the headline -- roofline, single-shot first step, CPU baseline, the literal trial loop,
+    the reference's own incremental metric, the set-only mode, configs[0] -- added to `out`."""
+    import torch.distributed as dist
+    from ipc_amd.consensus import IPC
+    from ipc_amd.dist import EngineBackend, ShardedMatrix
+    N = eng.N
+    out["roofline"], out["roofline_hbm"] = roofline_figures(args, g, cells, sms, launches, world)
     if ms_per_step < 5000.0:
         # A SINGLE-SHOT matrix: a second engine of the same graph (kernels loaded, streams there), its FIRST step -- the two
         # planning passes with their host read-back, the buffers' hipMalloc, cells solved in list order (the repeated steps
@@ -535,12 +489,6 @@ def main():
         out["first_step_note"] = ("single-shot matrix on a fresh engine: planning passes + host read-back + buffer allocation + cells in list "
                                   "order; ms_per_step is a repeated step on the cached cell lists (slow cells first)")
         eng1.close()
-    out["solved_cells_rank0"] = int(len(cells))
-    # cells whose intervals do not overlap cost nothing (C[i][j] = C[i][i] & C[j][j]): `value` counts them, as the metric
-    # is defined over all N(N+1)/2 pairs; the rate over the cells that are actually solved is the one to compare with
-    # cpu_baseline (which times solved cells only)
-    out["solved_cells_per_s"] = len(cells) * 1.0 / (ms_per_step * 1e-3) if world == 1 else None
-    out["free_cells_in_value"] = int(n_cells_total - len(cells)) if world == 1 else None
     if rank == 0 and world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(g, cfg, cells, args.cpu_seconds)
         gpu_solved_rate = len(cells) * 1.0 / (ms_per_step * 1e-3)
@@ -598,6 +546,114 @@ def main():
         # headline engine gone: every live engine holds streams, and beyond two dozen the runtime serialises them
         eng.close()
         out["incremental"]["configs0"] = faithful_run_of("C1")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed steps before them")
+    ap.add_argument("--workload", default="C2")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (float32 / float64, at most ~36 MB; rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline, single-shot first step, CPU baseline, GPU "
+                         "literal trial loop, the reference's incremental metric, set-only mode (minutes)")
+    ap.add_argument("--cpu-seconds", type=float, default=30.0, help="(--full) CPU baseline budget")
+    ap.add_argument("--no-cpu", action="store_true", help="(--full) skip the CPU baseline and the incremental metric")
+    ap.add_argument("--no-set-only", action="store_true", help="(--full) skip the set-only side measurement")
+    ap.add_argument("--incremental-candidates", type=int, default=None,
+                    help="(--full) candidates of the faithful incremental mode to time (reference metric); -1: all of them (C4: minutes, "
+                         "C5: tens of minutes -- one run instead of three); 0: none; default: all for C1 / C2 / tiny / T700 at 1 GPU, "
+                         "none otherwise")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        # plain `python bench.py --gpus N`: run N ranks (one per GPU) under torch.distributed.run in a child process
+        import socket
+        import subprocess
+        with socket.socket() as so:
+            so.bind(("127.0.0.1", 0))
+            port = so.getsockname()[1]
+        sys.exit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
+                                  "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
+                                  "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]))
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world != args.gpus:
+        raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
+    import torch.distributed as dist
+    from ipc_amd.consensus import IPC
+    from ipc_amd.dist import EngineBackend, ShardedMatrix
+
+    torch.cuda.set_device(local_rank)
+    if world > 1:
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        dist.init_process_group("nccl", rank=rank, world_size=world,
+                                device_id=torch.device("cuda", local_rank))
+
+    g, cfg, desc = build_workload(args.workload)
+    eng = IPC(g, cfg, device=local_rank)               # chain + candidates now resident in HBM
+    sm = ShardedMatrix(EngineBackend(eng), rank, world)
+    N = eng.N
+    n_cells_total = N * (N + 1) // 2
+
+    def barrier():
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+
+    for _ in range(args.warmup):
+        sm.step()
+    barrier()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        sm.step()
+    barrier()
+    dt = time.perf_counter() - t0
+    # per-step solver time from HIP events recorded on the launch stream (last step; --full's roofline)
+    sms, launches = eng.solver_time_ms()
+    if world > 1:
+        t = torch.tensor([dt], dtype=torch.float64, device="cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+    ms_per_step = dt / args.steps * 1e3
+
+    cells = eng.cell_info()                            # this rank's solved cells (of the last step)
+    bits, acc = sm.result()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, bits, acc, cells, N)
+
+    out = {
+        "metric": "candidate-pairs/s (consistency matrix + set-max)",
+        "value": n_cells_total * args.steps / dt,
+        "unit": "candidate-pairs/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": "%s: %s; N=%d candidates, %d cells (i<=j), %d solved on rank 0, "
+                               "s=%.0f, fast %.3f/%d, slow %.3f/%d" % (
+                                   args.workload, desc, N, n_cells_total, len(cells), cfg.s_factor,
+                                   cfg.fast_reject_th, cfg.fast_reject_iter_base, cfg.slow_reject_th,
+                                   cfg.slow_reject_iter_base),
+                   "parallelism": "rows%%%d + all-gather" % world if world > 1 else "1 GPU"},
+        "accepted": int(acc.sum()),
+    }
+    out["solved_cells_rank0"] = int(len(cells))
+    # cells whose intervals do not overlap cost nothing (C[i][j] = C[i][i] & C[j][j]): `value` counts them, as the metric
+    # is defined over all N(N+1)/2 pairs; the rate over the cells that are actually solved is the one to compare with
+    # cpu_baseline (which times solved cells only)
+    out["solved_cells_per_s"] = len(cells) * 1.0 / (ms_per_step * 1e-3) if world == 1 else None
+    out["free_cells_in_value"] = int(n_cells_total - len(cells)) if world == 1 else None
+    if args.full:
+        full_measurements(args, out, g, cfg, eng, acc, cells, sms, launches, ms_per_step, rank, local_rank, world, barrier)
     if rank == 0:
         print(json.dumps(out))
     if world > 1:

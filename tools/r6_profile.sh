@@ -19,7 +19,7 @@ for wl in $wls; do
   case $what in
   trace)
     rm -rf $out/trace_$w
-    rocprofv3 --kernel-trace --stats -d $out/trace_$w -o t -- python $root/bench.py --workload $wl --steps 3 --warmup 1 --no-cpu --no-set-only --incremental-candidates 0 > $out/r6_${w}_bench_traced.json 2> $out/trace_$w.log
+    rocprofv3 --kernel-trace --stats -d $out/trace_$w -o t -- python $root/bench.py --full --workload $wl --steps 3 --warmup 1 --no-cpu --no-set-only --incremental-candidates 0 > $out/r6_${w}_bench_traced.json 2> $out/trace_$w.log
     python $root/tools/rocpd_summary.py $(find $out/trace_$w -name "*.db" | head -1) > $out/r6_${w}_kernel_stats.csv
     rm -rf $out/trace_$w
     head -6 $out/r6_${w}_kernel_stats.csv | cut -c1-150; tail -1 $out/r6_${w}_kernel_stats.csv
