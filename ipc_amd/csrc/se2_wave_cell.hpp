@@ -168,9 +168,11 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
     const double term_scale = P.term_eps / (double)(L + NL);   // 0: the test is off
     bool lastGN = false;
     const int lane = threadIdx.x & 63;
-    const int wsub = W > 1 ? ((threadIdx.x >> 6) & (W - 1)) : 0;  // wave of the cell
+    // wave of the cell: the same in every lane, and said so (readfirstlane), so that what depends on it alone -- which
+    // mailbox rows to read, whose partial sum comes first -- is a scalar branch or select instead of an exec-mask skeleton
+    const int wsub = W > 1 ? (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) & (W - 1)) : 0;
     const int gl = wsub * 64 + lane;                 // lane index within the cell
-    const int j0 = gl * M + 1;                       // pose index of slot 0
+    int j0 = gl * M + 1;                             // pose index of slot 0 (not const: opaque() hides it)
 
     // ---- exchange among the W waves of the cell: every wave posts up to 8 doubles and waits for
     // all others; peer(o, k) then reads wave o's value k.  Also the cell's barrier. ----
@@ -343,14 +345,25 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
     // and the record-array padding cover)
     // The constants are loop-invariant, so the compiler would hoist every load out of the dog-leg
     // loop and pin 17 doubles per slot in registers; opaque() makes the index look modified, which
-    // keeps the loads where they are used.
+    // keeps the loads where they are used.  It hides two more per-lane values at every phase start:
+    //   * j0: the predicates built on it (pose exists, pose inside loop l: ~5 M 64-bit lane masks) are
+    //     then recomputed by a compare where they are used; hoisted out of the dog-leg loop they do not
+    //     fit the scalar registers and come back as two v_readlane each;
+    //   * the LDS address of the lane's first record, taken AFTER the window's base has been added: the
+    //     base (the cells' scratch precedes the window) is beyond the 8-bit offsets of a paired LDS read,
+    //     so with it left in the immediate every pair of loads paid a v_add_u32 of its own.
     int eloc = gl * M < L ? gl * M : 0;
-    auto opaque = [&]() { asm volatile("" : "+v"(eloc)); };
+    typedef const __attribute__((address_space(3))) double* LdsRec;
+    LdsRec crec = nullptr;
+    auto opaque = [&]() {
+        asm volatile("" : "+v"(eloc), "+v"(j0));
+        if (STAGED) { crec = (LdsRec)(cst + (lo_abs - wlo + eloc) * (int)F_SG); asm volatile("" : "+v"(crec)); }
+    };
     auto ldc = [&](int field, int s) -> double {
         // staged window: one record of F_SG doubles per edge, so a slot's constants sit at
         // compile-time offsets from ONE per-lane address (no address arithmetic, paired reads);
         // with M odd the lane stride of M * 88 bytes is bank-conflict free
-        if (STAGED && field < (int)F_SG) return cst[((lo_abs - wlo + eloc) + s) * (int)F_SG + field];
+        if (STAGED && field < (int)F_SG) return crec[s * (int)F_SG + field];
         // HBM / L2: record-major copy of the chain, so these loads too are compile-time offsets
         // from one per-lane address
         return P.chain_rec[((size_t)(lo_abs + eloc) + s) * (int)F_NFIELDS + field];
