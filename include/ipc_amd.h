@@ -100,6 +100,34 @@ int ipc_set_candidates(ipc_engine_t* h, int n, const int* ids, const double* mea
  * synchronisation.  *index_out = the new candidate's index. */
 int ipc_append_candidate(ipc_engine_t* h, const int* ids, const double* meas, const double* info, int* index_out);
 
+/* ---- online mode: the odometry chain grows in place -------------------------------------------------------------------
+ * The reference's constructor takes a loaded graph (src/consensus.cpp:13-23); nothing in IPC::agreementCheck needs the whole
+ * chain -- it reads the vertices up to the candidate's later one and re-propagates the tail.  A back end that meets its graph
+ * one pose at a time extends the engine instead of rebuilding it.
+ *
+ * ipc_append_odometry appends n_edges >= 1 odometry edges V-1 -> V, V -> V+1, ... (meas [n][3|7], info [n][6|21], as
+ * ipc_create).  For every new vertex: the chain record with its information scaled by s_factor (robustifyVoters,
+ * src/consensus_utils.cpp:124-130) in every copy the engine keeps; the open-loop pose open[V] = open[V-1] (+) z[V-1]
+ * (propagateGuess resumed, src/consensus_utils.cpp:99-116); and the current pose D (+) open[V] in the committed state and in every
+ * tentative state of the look-ahead pipeline, D being the rigid transform the last accept applied to that state's tail
+ * (propagateCurrentGuess, consensus_utils.cpp:61-71; a bit copy of open[V] before any accept and after ipc_incremental_reset).
+ * All of it is bit for bit what an engine created with the whole chain holds -- records, poses, and every ipc_check_info_t
+ * of the checks that follow.  After ipc_incremental_set_state there is no accept to take D from: D is then DEFINED from the
+ * handed-over poses the same way, T = poses[V-1], P = open[V-1], D = T (+) P^-1; the bitwise claim is for runs without a state
+ * injection after the last accept (the difference is rounding).
+ * Cost within the capacity, one edge: one small kernel that carries the record in its arguments, one over the pose states, an
+ * event the engine's other streams wait for before their next launch -- no allocation, no hipFree, no host synchronisation, the
+ * solves in flight and the cached plan of the matrix mode stay.  Several edges go through a pinned buffer of the engine.
+ * Beyond the capacity the arrays double (multiples of 64 vertices; the old ones are retired, not freed); a growth gives the
+ * look-ahead up and waits for the device, log2 V times over a run.
+ * ipc_reserve_vertices grows up front to `capacity` vertices (a caller that knows its mission length pays nothing later);
+ * a capacity below the current one is a no-op.  ipc_vertex_count: the vertex count of the moment -- what ipc_initial_poses,
+ * ipc_current_poses, ipc_incremental_set_state and ipc_final_optimize size their arrays by, and the bound on candidate ids.
+ * ipc_run_sharded keeps demanding engines of equal vertex count. */
+int ipc_append_odometry(ipc_engine_t* h, int n_edges, const double* meas, const double* info);
+int ipc_reserve_vertices(ipc_engine_t* h, int capacity);
+int ipc_vertex_count(ipc_engine_t* h, int* n_vertices);
+
 /* cmpTime processing order (host copy, N ints). */
 int ipc_candidate_order(ipc_engine_t* h, int* order_out);
 

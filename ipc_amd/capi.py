@@ -33,6 +33,7 @@ SYMBOLS = [
     "ipc_incremental_reset", "ipc_incremental_prepare", "ipc_agreement_check", "ipc_consensus_size", "ipc_consensus_set",
     "ipc_remove_from_consensus", "ipc_add_to_consensus", "ipc_current_poses", "ipc_final_optimize",
     "ipc_debug_dense_solve", "ipc_debug_band_solve", "ipc_debug_band_plan", "ipc_debug_absorbed_edges", "ipc_append_candidate", "ipc_incremental_set_state", "ipc_incremental_counters", "ipc_row_assignment", "ipc_run_sharded", "ipc_run_set_only",
+    "ipc_append_odometry", "ipc_reserve_vertices", "ipc_vertex_count",
 ]
 
 
@@ -97,6 +98,9 @@ def load():
     lib.ipc_destroy.argtypes = [vp]
     lib.ipc_set_candidates.argtypes = [vp, ip, vp, vp, vp]
     lib.ipc_append_candidate.argtypes = [vp, vp, vp, vp, C.POINTER(ip)]
+    lib.ipc_append_odometry.argtypes = [vp, ip, vp, vp]
+    lib.ipc_reserve_vertices.argtypes = [vp, ip]
+    lib.ipc_vertex_count.argtypes = [vp, C.POINTER(ip)]
     lib.ipc_candidate_order.argtypes = [vp, vp]
     lib.ipc_initial_poses.argtypes = [vp, vp]
     lib.ipc_rows_per_rank.argtypes = [ip, ip]

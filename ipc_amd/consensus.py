@@ -67,8 +67,29 @@ class IPC:
         k = C.c_int(-1)
         capi.check(self.lib.ipc_append_candidate(self.h, _p(ids), _p(meas), _p(info), C.byref(k)))
         self.N = k.value + 1
-        self.ids = np.vstack([self.ids, ids.reshape(1, 2)]) if self.N > 1 else ids.reshape(1, 2)
+        self.ids = np.vstack([self.ids, ids.reshape(1, 2)]) if self.N > 1 else ids.reshape(1, 2).copy()
         return k.value
+
+    # ---- online mode: the chain grows in place ---------------------------------------------
+    @property
+    def n_vertices(self):
+        """Vertex count of the moment (ipc_vertex_count): graph.V plus what append_odometry added."""
+        n = C.c_int(0)
+        capi.check(self.lib.ipc_vertex_count(self.h, C.byref(n)))
+        return n.value
+
+    def append_odometry(self, meas, info):
+        """Odometry edges V-1 -> V, V -> V+1, ... appended in place (ipc_append_odometry): meas [n, 3|7] (or one record),
+        info [n, 6|21].  Poses, consensus set and the solves in flight stay; returns the new vertex count."""
+        ms, ns = (3, 6) if self.dim == 2 else (7, 21)
+        meas, info = _d(meas).reshape(-1, ms), _d(info).reshape(-1, ns)
+        assert meas.shape[0] == info.shape[0]
+        capi.check(self.lib.ipc_append_odometry(self.h, int(meas.shape[0]), _p(meas), _p(info)))
+        return self.n_vertices
+
+    def reserve_vertices(self, n):
+        """Room for n vertices up front (ipc_reserve_vertices): appends up to there never grow the arrays."""
+        capi.check(self.lib.ipc_reserve_vertices(self.h, int(n)))
 
     def candidate_order(self):
         order = np.zeros(self.N, dtype=np.int32)
@@ -77,7 +98,7 @@ class IPC:
 
     def initial_poses(self):
         ps = 3 if self.dim == 2 else 12
-        out = np.zeros((self.graph.V, ps))
+        out = np.zeros((self.n_vertices, ps))
         capi.check(self.lib.ipc_initial_poses(self.h, _p(out)))
         return out
 
@@ -148,7 +169,7 @@ class IPC:
         self._max_consensus_set = self._consensus()
 
     def current_poses(self):
-        out = np.zeros((self.graph.V, 3 if self.dim == 2 else 12))
+        out = np.zeros((self.n_vertices, 3 if self.dim == 2 else 12))
         capi.check(self.lib.ipc_current_poses(self.h, _p(out)))
         return out
 
@@ -156,7 +177,7 @@ class IPC:
         """Resume the agreementCheck loop from a saved (current_poses(), getMaxConsensusSet()) pair
         (ipc_incremental_set_state; the two are all the state of reference include/ipc/consensus.hpp:23-32)."""
         poses = _d(poses)
-        assert poses.shape == (self.graph.V, 3 if self.dim == 2 else 12)
+        assert poses.shape == (self.n_vertices, 3 if self.dim == 2 else 12)
         cns = np.ascontiguousarray(consensus, dtype=np.int32)
         capi.check(self.lib.ipc_incremental_set_state(self.h, _p(poses), _p(cns), int(cns.shape[0]), int(resume_position)))
         self._max_consensus_set = cns.copy()
@@ -171,7 +192,7 @@ class IPC:
         """The harness's final map (reference src/simulation.cpp:50-65): returns (poses [V,3] or
         [V,12] (R row-major, t), CheckInfo with chi2_total)."""
         acc = np.ascontiguousarray(accepted, dtype=np.uint8)
-        out = np.zeros((self.graph.V, 3 if self.dim == 2 else 12))
+        out = np.zeros((self.n_vertices, 3 if self.dim == 2 else 12))
         info = capi.CheckInfo()
         capi.check(self.lib.ipc_final_optimize(self.h, _p(acc), int(iterations), _p(out), C.byref(info)))
         return out, info

@@ -125,19 +125,26 @@ __global__ void k_records(int n, int nf, const double* rec, int stride, double* 
 // propagateGuess (reference src/consensus_utils.cpp:99-116): v0 at origin, v[i] = v[i-1] * z[i-1]
 // (SE2::operator*: t += R t2, theta = normalize(theta + theta2)).  Sequential by nature and run
 // once per engine, so a single lane walks the chain.
-__global__ void k_se2_propagate(int V, const double* rec, int stride, double* pose0)
+// One step of it, v[i] = v[i-1] * z[i-1] with z = edge i-1 of `rec`: shared with k_append_odometry, which resumes the
+// chain of compositions from the stored v[V-1] (the loop carries nothing but x, y, theta from one step to the next).
+__device__ __forceinline__ void se2_compose_step(double& x, double& y, double& th, const double* rec, int stride, int i)
+{
+    double s, c;
+    sincos(th, &s, &c);
+    const double tx = rec[(size_t)F_TZX * stride + i - 1], ty = rec[(size_t)F_TZY * stride + i - 1];
+    x += c * tx - s * ty;
+    y += s * tx + c * ty;
+    th = normalize_theta(th + rec[(size_t)F_THZ * stride + i - 1]);
+}
+// pose0 = [3][vs], vs >= V: the stride of the pose arrays is their capacity, not the vertex count
+__global__ void k_se2_propagate(int V, const double* rec, int stride, double* pose0, int vs)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     double x = 0, y = 0, th = 0;
-    pose0[0] = x; pose0[V] = y; pose0[2 * (size_t)V] = th;
+    pose0[0] = x; pose0[vs] = y; pose0[2 * (size_t)vs] = th;
     for (int i = 1; i < V; ++i) {
-        double s, c;
-        sincos(th, &s, &c);
-        const double tx = rec[(size_t)F_TZX * stride + i - 1], ty = rec[(size_t)F_TZY * stride + i - 1];
-        x += c * tx - s * ty;
-        y += s * tx + c * ty;
-        th = normalize_theta(th + rec[(size_t)F_THZ * stride + i - 1]);
-        pose0[i] = x; pose0[(size_t)V + i] = y; pose0[2 * (size_t)V + i] = th;
+        se2_compose_step(x, y, th, rec, stride, i);
+        pose0[i] = x; pose0[(size_t)vs + i] = y; pose0[2 * (size_t)vs + i] = th;
     }
 }
 
@@ -213,10 +220,8 @@ __global__ void k_prep_one(RawCandidate r, int k, double* rec, int stride, int* 
 
 // field-major SE3 records -> blocks of 64 edges x kSe3BlkPairs double2 (se3_lds_cell.hpp reads them with
 // one coalesced 16-byte load per lane): pairs 0..5 = Rz, tz; 6..16 = information (+ pad); 17..27 = covariance (+ pad)
-__global__ void k_se3_blocks(int n, const double* rec, int stride, double2* out)
+__device__ __forceinline__ void se3_block_record(const double* rec, int stride, double2* out, int k)
 {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
     double2* o = out + (size_t)(k >> 6) * (kSe3BlkPairs * 64) + (k & 63);
     auto F = [&](int f) { return rec[(size_t)f * stride + k]; };
     for (int p = 0; p < 6; ++p) o[p * 64] = make_double2(F(2 * p), F(2 * p + 1));
@@ -225,24 +230,34 @@ __global__ void k_se3_blocks(int n, const double* rec, int stride, double2* out)
         o[(17 + p) * 64] = make_double2(F(G_SG + 2 * p), 2 * p + 1 < 21 ? F(G_SG + 2 * p + 1) : 0.0);
     }
 }
+__global__ void k_se3_blocks(int n, const double* rec, int stride, double2* out)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    se3_block_record(rec, stride, out, k);
+}
 
 // propagateGuess for SE3: v0 = identity, v[i] = v[i-1] * z[i-1] (Isometry3 product)
-__global__ void k_se3_propagate(int V, const double* rec, int stride, double* pose0)
+__device__ __forceinline__ void se3_compose_step(double* R, double* t, const double* rec, int stride, int i)
+{
+    double Rz[9], tz[3], Rn[9], d[3];
+    for (int q = 0; q < 9; ++q) Rz[q] = rec[(size_t)(G_RZ + q) * stride + i - 1];
+    for (int q = 0; q < 3; ++q) tz[q] = rec[(size_t)(G_TZ + q) * stride + i - 1];
+    m3_mul(R, Rz, Rn);
+    m3_vec(R, tz, d);
+    for (int q = 0; q < 3; ++q) t[q] += d[q];
+    for (int q = 0; q < 9; ++q) R[q] = Rn[q];
+}
+__global__ void k_se3_propagate(int V, const double* rec, int stride, double* pose0, int vs)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
-    for (int q = 0; q < 9; ++q) pose0[(size_t)q * V] = R[q];
-    for (int q = 0; q < 3; ++q) pose0[(size_t)(9 + q) * V] = t[q];
+    for (int q = 0; q < 9; ++q) pose0[(size_t)q * vs] = R[q];
+    for (int q = 0; q < 3; ++q) pose0[(size_t)(9 + q) * vs] = t[q];
     for (int i = 1; i < V; ++i) {
-        double Rz[9], tz[3], Rn[9], d[3];
-        for (int q = 0; q < 9; ++q) Rz[q] = rec[(size_t)(G_RZ + q) * stride + i - 1];
-        for (int q = 0; q < 3; ++q) tz[q] = rec[(size_t)(G_TZ + q) * stride + i - 1];
-        m3_mul(R, Rz, Rn);
-        m3_vec(R, tz, d);
-        for (int q = 0; q < 3; ++q) t[q] += d[q];
-        for (int q = 0; q < 9; ++q) R[q] = Rn[q];
-        for (int q = 0; q < 9; ++q) pose0[(size_t)q * V + i] = R[q];
-        for (int q = 0; q < 3; ++q) pose0[(size_t)(9 + q) * V + i] = t[q];
+        se3_compose_step(R, t, rec, stride, i);
+        for (int q = 0; q < 9; ++q) pose0[(size_t)q * vs + i] = R[q];
+        for (int q = 0; q < 3; ++q) pose0[(size_t)(9 + q) * vs + i] = t[q];
     }
 }
 
@@ -568,14 +583,20 @@ static hipError_t launch_se3_lds(int nl, int idx, int n, hipStream_t st, const S
 
 struct ipc_engine {
     int dim = 2, V = 0, N = 0, device = 0;
+    // V is the vertex COUNT of the moment; the pose arrays ([3 | 5 | 12][vcap]) are addressed by their capacity vcap >= V and
+    // the chain arrays by estride >= V - 1, so that ipc_append_odometry grows the chain in place (DESIGN.md "Online chain")
+    int vcap = 0;
+    double* h_stage = nullptr; double* d_stage = nullptr; size_t stage_cap = 0;   // pinned staging of an append of several edges
+    hipEvent_t ev_stage = nullptr; bool stage_used = false;                       // behind the kernel that read it last
+    long chain_growths = 0;
     ipc_params_t prm{};
     double term_eps = 1e-13;                           // IPC_TERMINATE_EPS (0: g2o's literal trial loop), Se2View::term_eps
     BinPlan plan{};
     hipStream_t own_stream = nullptr;
     // chain
     double* d_chain = nullptr; int estride = 0;
-    double* d_chain_rec = nullptr;                     // record-major copy [E + 64][F_NFIELDS | G_NFIELDS]
-    double2* d_chain_blk = nullptr;                    // SE3: blocked copy [E / 64 + 2][kSe3BlkPairs][64]
+    double* d_chain_rec = nullptr;                     // record-major copy [estride + 64][F_NFIELDS | G_NFIELDS]
+    double2* d_chain_blk = nullptr;                    // SE3: blocked copy [estride / 64 + 2][kSe3BlkPairs][64]
     double* d_pose0 = nullptr;
     // candidates
     double* d_cand = nullptr; int cstride = 0;        // cstride = capacity in records (>= N): the list grows in place
@@ -620,8 +641,8 @@ struct ipc_engine {
     std::vector<double> h_odom_meas, h_odom_info;      // file values, for the un-scaled chain
     std::vector<int> h_from, h_to, cns;
     double* d_chain1 = nullptr;                        // chain records with (info * s) / s
-    double* d_open = nullptr;                          // [5][V] open-loop x y th cos sin
-    double* d_cur = nullptr;                           // [5][V] current estimates
+    double* d_open = nullptr;                          // [5][vcap] open-loop x y th cos sin
+    double* d_cur = nullptr;                           // [5][vcap] current estimates + kPoseTrail doubles (the tail transform, k_apply_accept)
     ClusterSolver2* cluster = nullptr;
     ClusterSolver3* cluster3 = nullptr;                // SE3: d_open is d_pose0 itself, d_cur is [12][V]
     // device-resident dog-leg (cluster_persist.hpp): the default; IPC_CLUSTER_MODE=host keeps the host-driven kernels
@@ -670,7 +691,7 @@ struct ipc_engine {
         double pred_ratio = -1.0;                      // the candidate's own chi2 at the state it starts from / the slow threshold (IPC_SPEC_LOG)
     };
     struct SpecState {                                 // a pose state solves start from
-        double* d_poses = nullptr;                     // d_cur (not owned) or a buffer of its own, [5 | 12][V]
+        double* d_poses = nullptr;                     // d_cur (not owned) or a buffer of its own, [5 | 12][vcap] + kPoseTrail
         bool owned = false;
         hipEvent_t ready = nullptr;                    // its poses are complete (recorded on the stream that wrote them)
         bool has_ready = false;
@@ -800,6 +821,16 @@ static hipError_t copy_d2d_now(ipc_engine* h, void* dst, const void* src, size_t
     hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, h->own_stream);
     return e != hipSuccess ? e : hipStreamSynchronize(h->own_stream);
 }
+// Current poses = open-loop poses, and no tail transform (k_apply_accept): the state right after IPC::IPC.
+constexpr int kPoseTrail = 16;                         // doubles behind a pose state's [5 | 12][vcap]: the transform D, [15] = 1.0 once an accept wrote it
+static int reset_current(ipc_engine* h)
+{
+    const size_t n = (h->dim == 2 ? 5 : 12) * (size_t)h->vcap;
+    HIPCHK(hipMemcpyAsync(h->d_cur, h->d_open, sizeof(double) * n, hipMemcpyDeviceToDevice, h->own_stream));
+    HIPCHK(hipMemsetAsync(h->d_cur + n, 0, sizeof(double) * kPoseTrail, h->own_stream));
+    HIPCHK(hipStreamSynchronize(h->own_stream));
+    return IPC_OK;
+}
 extern "C" int ipc_rows_per_rank(int n, int world) { return world > 0 ? (n + world - 1) / world : 0; }
 
 // Which rank solves which row, and where the row sits in that rank's shard: slot[i] = owner * rpr + index, rpr =
@@ -870,7 +901,7 @@ extern "C" int ipc_create(int dim, int n_vertices, const double* odom_meas, cons
     if (device < 0 || device >= ndev) return fail(IPC_ERR_ARG, "ipc_create: device %d of %d", device, ndev);
     HIPCHK(hipSetDevice(device));
     ipc_engine* h = new ipc_engine();
-    h->dim = dim; h->V = n_vertices; h->prm = *params; h->device = device;
+    h->dim = dim; h->V = h->vcap = n_vertices; h->prm = *params; h->device = device;
     {
         std::string perr;
         if (!make_plan(h->plan, dim, perr)) { delete h; return fail(IPC_ERR_ARG, "%s", perr.c_str()); }
@@ -973,21 +1004,21 @@ extern "C" int ipc_create(int dim, int n_vertices, const double* odom_meas, cons
         hipLaunchKernelGGL(k_se2_prep, dim3((E + 255) / 256), dim3(256), 0, h->own_stream, E, d_m, d_i,
                            params->s_factor, h->d_chain, h->estride);
         hipLaunchKernelGGL(k_se2_propagate, dim3(1), dim3(64), 0, h->own_stream, n_vertices, h->d_chain, h->estride,
-                           h->d_pose0);
-        HIPCHK(hipMalloc(&h->d_chain_rec, sizeof(double) * (size_t)F_NFIELDS * (E + 64)));
-        HIPCHK(hipMemsetAsync(h->d_chain_rec, 0, sizeof(double) * (size_t)F_NFIELDS * (E + 64), h->own_stream));
+                           h->d_pose0, h->vcap);
+        HIPCHK(hipMalloc(&h->d_chain_rec, sizeof(double) * (size_t)F_NFIELDS * (h->estride + 64)));
+        HIPCHK(hipMemsetAsync(h->d_chain_rec, 0, sizeof(double) * (size_t)F_NFIELDS * (h->estride + 64), h->own_stream));
         hipLaunchKernelGGL(k_records, dim3((E + 255) / 256), dim3(256), 0, h->own_stream, E, (int)F_NFIELDS, h->d_chain,
                            h->estride, h->d_chain_rec);
     } else {
         hipLaunchKernelGGL(k_se3_prep, dim3((E + 63) / 64), dim3(64), 0, h->own_stream, E, d_m, d_i,
                            params->s_factor, h->d_chain, h->estride);
         hipLaunchKernelGGL(k_se3_propagate, dim3(1), dim3(64), 0, h->own_stream, n_vertices, h->d_chain, h->estride,
-                           h->d_pose0);
-        HIPCHK(hipMalloc(&h->d_chain_rec, sizeof(double) * (size_t)G_NFIELDS * (E + 64)));
-        HIPCHK(hipMemsetAsync(h->d_chain_rec, 0, sizeof(double) * (size_t)G_NFIELDS * (E + 64), h->own_stream));
+                           h->d_pose0, h->vcap);
+        HIPCHK(hipMalloc(&h->d_chain_rec, sizeof(double) * (size_t)G_NFIELDS * (h->estride + 64)));
+        HIPCHK(hipMemsetAsync(h->d_chain_rec, 0, sizeof(double) * (size_t)G_NFIELDS * (h->estride + 64), h->own_stream));
         hipLaunchKernelGGL(k_records, dim3((E + 255) / 256), dim3(256), 0, h->own_stream, E, (int)G_NFIELDS, h->d_chain,
                            h->estride, h->d_chain_rec);
-        const size_t nblk = (size_t)(E + 63) / 64 + 2;
+        const size_t nblk = (size_t)h->estride / 64 + 2;
         HIPCHK(hipMalloc(&h->d_chain_blk, sizeof(double2) * nblk * kSe3BlkPairs * 64));
         HIPCHK(hipMemsetAsync(h->d_chain_blk, 0, sizeof(double2) * nblk * kSe3BlkPairs * 64, h->own_stream));
         hipLaunchKernelGGL(k_se3_blocks, dim3((E + 255) / 256), dim3(256), 0, h->own_stream, E, h->d_chain, h->estride,
@@ -1074,6 +1105,8 @@ extern "C" int ipc_destroy(ipc_engine_t* h)
     hipFree(h->d_upper); hipFree(h->d_bits); hipFree(h->d_acc); hipFree(h->d_failed);
     hipFree(h->d_lit_cells); hipFree(h->d_lit_idx); hipFree(h->d_lit_chi); hipFree(h->d_lit_chitot); hipFree(h->d_lit_meta);
     hipFree(h->d_slot_off); hipFree(h->d_recount); if (h->h_recount) hipHostFree(h->h_recount);
+    if (h->h_stage) hipHostFree(h->h_stage);
+    if (h->ev_stage) hipEventDestroy(h->ev_stage);
     hipFree(h->d_chain1); if (h->d_open != h->d_pose0) hipFree(h->d_open); hipFree(h->d_cur);
     delete h->cluster;
     delete h->cluster3;
@@ -1157,8 +1190,7 @@ static int upload_candidates(ipc_engine* h, int n, const int* ids, const double*
     h->plan_cached = false;
     h->ev_valid = false;
     h->cns.clear(); h->cns_dups = false;
-    if (h->d_cur && h->d_open)
-        HIPCHK(copy_d2d_now(h, h->d_cur, h->d_open, sizeof(double) * (h->dim == 2 ? 5 : 12) * (size_t)h->V));
+    if (h->d_cur && h->d_open) { if (int rc = reset_current(h)) return rc; }
     const int ms = h->dim == 2 ? 3 : 7, is = h->dim == 2 ? 6 : 21;
     h->h_cand_ids.assign(ids, ids + 2 * (size_t)n);                       // raw records (row assignment, appends)
     h->h_cand_meas.assign(meas, meas + (size_t)ms * n);
@@ -1301,8 +1333,9 @@ extern "C" int ipc_initial_poses(ipc_engine_t* h, double* poses_out)
     if (!h || !poses_out) return fail(IPC_ERR_ARG, "ipc_initial_poses: NULL argument");
     HIPCHK(hipSetDevice(h->device));
     const int ps = h->dim == 2 ? 3 : 12;
+    HIPCHK(hipStreamSynchronize(h->own_stream));               // (poses ipc_append_odometry is still writing)
     std::vector<double> tmp(ps * (size_t)h->V);
-    HIPCHK(hipMemcpy(tmp.data(), h->d_pose0, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy2D(tmp.data(), sizeof(double) * h->V, h->d_pose0, sizeof(double) * h->vcap, sizeof(double) * h->V, ps, hipMemcpyDeviceToHost));
     for (int i = 0; i < h->V; ++i)
         for (int f = 0; f < ps; ++f) poses_out[ps * (size_t)i + f] = tmp[(size_t)f * h->V + i];
     return IPC_OK;
@@ -1323,7 +1356,7 @@ static double* dbg_buffer()
 static Se2View make_view(const ipc_engine* h)
 {
     Se2View P;
-    P.chain = h->d_chain; P.estride = h->estride; P.pose0 = h->d_pose0; P.V = h->V;
+    P.chain = h->d_chain; P.estride = h->estride; P.pose0 = h->d_pose0; P.V = h->V; P.VS = h->vcap;
     P.chain_rec = h->d_chain_rec;
     P.cand = h->d_cand; P.cstride = h->cstride; P.cand_from = h->d_from; P.cand_to = h->d_to;
     P.dbg = dbg_buffer();
@@ -1334,7 +1367,7 @@ static Se2View make_view(const ipc_engine* h)
 static Se3View make_view3(const ipc_engine* h)
 {
     Se3View P;
-    P.chain = h->d_chain; P.estride = h->estride; P.pose0 = h->d_pose0; P.V = h->V;
+    P.chain = h->d_chain; P.estride = h->estride; P.pose0 = h->d_pose0; P.V = h->V; P.VS = h->vcap;
     P.chain_rec = h->d_chain_rec;
     P.chain_blk = h->d_chain_blk;
     P.term_eps = h->term_eps;
@@ -1364,12 +1397,12 @@ static hipError_t cluster_solve(ipc_engine* h, const double* chain, double* src,
         bool lost = false;
         for (int attempt = 0; attempt < 3; ++attempt) {
             if (h->dim == 3) {
-                IPC_CL_CHK(h->persist3->launch(h->own_stream, chain, h->estride, h->d_cand, h->cstride, src, h->V, lo, hi, members,
+                IPC_CL_CHK(h->persist3->launch(h->own_stream, chain, h->estride, h->d_cand, h->cstride, src, h->vcap, lo, hi, members,
                                                h->h_from.data(), h->h_to.data(), iters));
                 IPC_CL_CHK(h->persist3->wait(o));
                 lost = h->persist3->timed_out();
             } else {
-                IPC_CL_CHK(h->persist2->launch(h->own_stream, chain, h->estride, h->d_cand, h->cstride, src, h->V, lo, hi, members,
+                IPC_CL_CHK(h->persist2->launch(h->own_stream, chain, h->estride, h->d_cand, h->cstride, src, h->vcap, lo, hi, members,
                                                h->h_from.data(), h->h_to.data(), iters));
                 IPC_CL_CHK(h->persist2->wait(o));
                 lost = h->persist2->timed_out();
@@ -1386,9 +1419,9 @@ static hipError_t cluster_solve(ipc_engine* h, const double* chain, double* src,
         ++h->lm_fallbacks;
     }
     if (h->dim == 3)
-        return h->cluster3->solve(h->own_stream, chain, h->estride, h->d_cand, h->cstride, src, h->V, lo, hi, members,
+        return h->cluster3->solve(h->own_stream, chain, h->estride, h->d_cand, h->cstride, src, h->vcap, lo, hi, members,
                                   h->h_from.data(), h->h_to.data(), iters, o, nullptr);
-    return h->cluster->solve(h->own_stream, chain, h->estride, h->d_cand, h->cstride, pose_arr(src, h->V), lo, hi, members,
+    return h->cluster->solve(h->own_stream, chain, h->estride, h->d_cand, h->cstride, pose_arr(src, h->vcap), lo, hi, members,
                              h->h_from.data(), h->h_to.data(), iters, o, nullptr);
 }
 static PoseArr cluster_result2(const ipc_engine* h)
@@ -2002,15 +2035,16 @@ extern "C" int ipc_synchronize(ipc_engine_t* h)
 // ------------------------------------------------------------------------------------------
 // faithful incremental mode + final map, SE2
 // ------------------------------------------------------------------------------------------
-__global__ void k_pose5_init(int V, const double* pose0, double* out)
+// pose0 = [3][is] -> out = [5][os], vertices first .. V-1
+__global__ void k_pose5_init(int V, const double* pose0, int is, double* out, int os, int first = 0)
 {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = first + blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= V) return;
-    const double th = pose0[2 * (size_t)V + i];
+    const double th = pose0[2 * (size_t)is + i];
     double s, c;
     sincos_pi(th, s, c);
-    out[i] = pose0[i]; out[(size_t)V + i] = pose0[(size_t)V + i]; out[2 * (size_t)V + i] = th;
-    out[3 * (size_t)V + i] = c; out[4 * (size_t)V + i] = s;
+    out[i] = pose0[i]; out[(size_t)os + i] = pose0[(size_t)is + i]; out[2 * (size_t)os + i] = th;
+    out[3 * (size_t)os + i] = c; out[4 * (size_t)os + i] = s;
 }
 
 // propagateCurrentGuess (reference src/consensus_utils.cpp:61-71): v[i] = v[i-1] * z[i-1] for
@@ -2088,55 +2122,199 @@ __global__ void k_cand_own_chi2_se3(const double* poses, int V, const double* ca
 // on C2's trajectory, on the critical path of everything behind the accept).  The two forms differ by rounding only.
 // NF = 5 (SE2: x, y, theta, cos, sin; open = [5][V]) or 12 (SE3: R row-major, t; open = [12][V]); X = the solver's
 // arrays [NF][ldx], window index 0 = lo.
+// The transform is also STORED with the state it was applied to (kPoseTrail doubles behind dst's [NF][vs]: SE2 x, y, theta, cos,
+// sin of D; SE3 R_D, t_D; [15] = 1.0), and computed when the tail is empty too: a vertex appended later
+// (ipc_append_odometry) is D (+) open[V] with the same D, i.e. bit for bit what this kernel would have written had the
+// vertex been there.  V = vertices, vs = stride of parent / open / dst.
+__device__ __forceinline__ void se2_tail_D(double xT, double yT, double thT, const double* open, size_t Vs, int hi, double* D)
+{
+    // D = T (+) P^-1: theta_D = theta_T - theta_P, t_D = t_T - R_D t_P
+    const double thP = open[2 * Vs + hi];
+    const double thD = normalize_theta(thT - thP);
+    double sD, cD;
+    sincos_pi(thD, sD, cD);
+    const double xP = open[hi], yP = open[Vs + hi];
+    const double xD = xT - (cD * xP - sD * yP), yD = yT - (sD * xP + cD * yP);
+    D[0] = xD; D[1] = yD; D[2] = thD; D[3] = cD; D[4] = sD;
+}
+__device__ __forceinline__ void se2_tail_apply(const double* D, const double* open, size_t Vs, double* dst, int i)
+{
+    const double xD = D[0], yD = D[1], thD = D[2], cD = D[3], sD = D[4];
+    const double x = open[i], y = open[Vs + i];
+    const double th = normalize_theta(thD + open[2 * Vs + i]);
+    double sn, cs;
+    sincos_pi(th, sn, cs);
+    dst[i] = xD + (cD * x - sD * y);
+    dst[Vs + i] = yD + (sD * x + cD * y);
+    dst[2 * Vs + i] = th;
+    dst[3 * Vs + i] = cs;
+    dst[4 * Vs + i] = sn;
+}
+// T = [12] values at stride ldt (R row-major, t)
+__device__ __forceinline__ void se3_tail_D(const double* T, size_t ldt, const double* open, size_t Vs, int hi, double* D)
+{
+    double RT[9], tT[3], RP[9], tP[3], d[3];
+    double* RD = D;
+    for (int q = 0; q < 9; ++q) { RT[q] = T[(size_t)q * ldt]; RP[q] = open[(size_t)q * Vs + hi]; }
+    for (int q = 0; q < 3; ++q) { tT[q] = T[(size_t)(9 + q) * ldt]; tP[q] = open[(size_t)(9 + q) * Vs + hi]; }
+    for (int r = 0; r < 3; ++r)                             // R_D = R_T R_P^T
+        for (int c = 0; c < 3; ++c) RD[3 * r + c] = RT[3 * r] * RP[3 * c] + RT[3 * r + 1] * RP[3 * c + 1] + RT[3 * r + 2] * RP[3 * c + 2];
+    m3_vec(RD, tP, d);
+    for (int q = 0; q < 3; ++q) D[9 + q] = tT[q] - d[q];
+}
+__device__ __forceinline__ void se3_tail_apply(const double* D, const double* open, size_t Vs, double* dst, int i)
+{
+    const double* RD = D;
+    const double* tD = D + 9;
+    double Ri[9], ti[3], Rn[9], d[3];
+    for (int q = 0; q < 9; ++q) Ri[q] = open[(size_t)q * Vs + i];
+    for (int q = 0; q < 3; ++q) ti[q] = open[(size_t)(9 + q) * Vs + i];
+    m3_mul(RD, Ri, Rn);
+    m3_vec(RD, ti, d);
+    for (int q = 0; q < 9; ++q) dst[(size_t)q * Vs + i] = Rn[q];
+    for (int q = 0; q < 3; ++q) dst[(size_t)(9 + q) * Vs + i] = tD[q] + d[q];
+}
 template <int NF>
-__global__ __launch_bounds__(256) void k_apply_accept(int V, int lo, int hi, const double* parent, const double* X, int ldx,
+__global__ __launch_bounds__(256) void k_apply_accept(int V, int vs, int lo, int hi, const double* parent, const double* X, int ldx,
                                                       const double* open, double* dst)
 {
     const int tid = threadIdx.x;
     for (int q = tid; q < NF * V; q += 256) {
         const int f = q / V, i = q - f * V;
-        if (i >= lo && i <= hi) dst[q] = X[(size_t)f * ldx + (i - lo)];
-        else if (i < lo && dst != parent) dst[q] = parent[q];
+        const size_t a = (size_t)f * vs + i;
+        if (i >= lo && i <= hi) dst[a] = X[(size_t)f * ldx + (i - lo)];
+        else if (i < lo && dst != parent) dst[a] = parent[a];
     }
-    if (hi + 1 >= V) return;
-    const size_t Vs = (size_t)V;
-    if (NF == 5) {
-        // D = T (+) P^-1: theta_D = theta_T - theta_P, t_D = t_T - R_D t_P
-        const double thT = X[2 * (size_t)ldx + (hi - lo)], thP = open[2 * Vs + hi];
-        const double thD = normalize_theta(thT - thP);
-        double sD, cD;
-        sincos_pi(thD, sD, cD);
-        const double xP = open[hi], yP = open[Vs + hi];
-        const double xD = X[hi - lo] - (cD * xP - sD * yP), yD = X[(size_t)ldx + (hi - lo)] - (sD * xP + cD * yP);
-        for (int i = hi + 1 + tid; i < V; i += 256) {
-            const double x = open[i], y = open[Vs + i];
-            const double th = normalize_theta(thD + open[2 * Vs + i]);
-            double sn, cs;
-            sincos_pi(th, sn, cs);
-            dst[i] = xD + (cD * x - sD * y);
-            dst[Vs + i] = yD + (sD * x + cD * y);
-            dst[2 * Vs + i] = th;
-            dst[3 * Vs + i] = cs;
-            dst[4 * Vs + i] = sn;
+    const size_t Vs = (size_t)vs;
+    double D[12];
+    if (NF == 5) se2_tail_D(X[hi - lo], X[(size_t)ldx + (hi - lo)], X[2 * (size_t)ldx + (hi - lo)], open, Vs, hi, D);
+    else se3_tail_D(X + (hi - lo), (size_t)ldx, open, Vs, hi, D);
+    if (tid == 0) {
+        double* tr = dst + (size_t)NF * Vs;
+        for (int q = 0; q < NF; ++q) tr[q] = D[q];
+        tr[kPoseTrail - 1] = 1.0;
+    }
+    for (int i = hi + 1 + tid; i < V; i += 256) {
+        if (NF == 5) se2_tail_apply(D, open, Vs, dst, i);
+        else se3_tail_apply(D, open, Vs, dst, i);
+    }
+}
+// ipc_incremental_set_state has no accept to take D from: it is defined from the handed-over poses the same way, T = poses[V-1],
+// P = open[V-1] (include/ipc_amd.h)
+template <int NF>
+__global__ void k_state_D(int V, int vs, const double* open, double* cur)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const size_t Vs = (size_t)vs;
+    double D[12];
+    if (NF == 5) se2_tail_D(cur[V - 1], cur[Vs + V - 1], cur[2 * Vs + V - 1], open, Vs, V - 1, D);
+    else se3_tail_D(cur + (V - 1), Vs, open, Vs, V - 1, D);
+    double* tr = cur + (size_t)NF * Vs;
+    for (int q = 0; q < NF; ++q) tr[q] = D[q];
+    tr[kPoseTrail - 1] = 1.0;
+}
+
+// ---- ipc_append_odometry: the chain grows in place --------------------------------------------------------------------
+// Every copy of the chain the engine keeps, all addressed by a capacity (estride / vs), never by the edge count.
+struct ChainPtrs {
+    double* chain; int estride;                        // field-major records, information * s_factor
+    double* chain_rec;                                 // record-major copy
+    double2* chain_blk;                                // SE3: blocked copy
+    double* chain1;                                    // (info * s) / s, the final map's records; NULL until ipc_final_optimize made them
+    double* pose0;                                     // [3 | 12][vs] open-loop poses
+    double* open5;                                     // SE2: [5][vs] open-loop x y th cos sin; NULL until the incremental mode made it
+    int vs;
+};
+struct RawOdometry { double meas[7]; double info[21]; };   // one raw record, 224 B of kernel arguments (the RawCandidate pattern)
+// edge k: what k_se2_prep / k_se3_prep, k_records and k_se3_blocks write at create time
+template <int DIM>
+__device__ __forceinline__ void append_edge_records(const double* m, const double* inf, double scale, const ChainPtrs& C, int k)
+{
+    constexpr int nf = DIM == 2 ? (int)F_NFIELDS : (int)G_NFIELDS;
+    if (DIM == 2) se2_prep_record(m, inf, scale, 1.0, C.chain, C.estride, k);
+    else se3_prep_record(m, inf, scale, 1.0, C.chain, C.estride, k);
+    for (int f = 0; f < nf; ++f) C.chain_rec[(size_t)k * nf + f] = C.chain[(size_t)f * C.estride + k];
+    if (DIM == 3) se3_block_record(C.chain, C.estride, C.chain_blk, k);
+    if (C.chain1) {
+        if (DIM == 2) se2_prep_record(m, inf, scale, scale, C.chain1, C.estride, k);
+        else se3_prep_record(m, inf, scale, scale, C.chain1, C.estride, k);
+    }
+}
+// vertices V0 .. V0 + n - 1: open[i] = open[i-1] (+) z[i-1], the loop of k_se2_propagate / k_se3_propagate resumed from the
+// stored open[V0 - 1] (one lane: sequential by nature)
+template <int DIM>
+__device__ __forceinline__ void append_compose(int V0, int n, const ChainPtrs& C)
+{
+    const size_t vs = (size_t)C.vs;
+    if (DIM == 2) {
+        double x = C.pose0[V0 - 1], y = C.pose0[vs + V0 - 1], th = C.pose0[2 * vs + V0 - 1];
+        for (int i = V0; i < V0 + n; ++i) {
+            se2_compose_step(x, y, th, C.chain, C.estride, i);
+            C.pose0[i] = x; C.pose0[vs + i] = y; C.pose0[2 * vs + i] = th;
+            if (C.open5) {                                   // as k_pose5_init
+                double s, c;
+                sincos_pi(th, s, c);
+                C.open5[i] = x; C.open5[vs + i] = y; C.open5[2 * vs + i] = th; C.open5[3 * vs + i] = c; C.open5[4 * vs + i] = s;
+            }
         }
     } else {
-        double RT[9], tT[3], RP[9], tP[3], RD[9], tD[3], d[3];
-        for (int q = 0; q < 9; ++q) { RT[q] = X[(size_t)q * ldx + (hi - lo)]; RP[q] = open[(size_t)q * Vs + hi]; }
-        for (int q = 0; q < 3; ++q) { tT[q] = X[(size_t)(9 + q) * ldx + (hi - lo)]; tP[q] = open[(size_t)(9 + q) * Vs + hi]; }
-        for (int r = 0; r < 3; ++r)                             // R_D = R_T R_P^T
-            for (int c = 0; c < 3; ++c) RD[3 * r + c] = RT[3 * r] * RP[3 * c] + RT[3 * r + 1] * RP[3 * c + 1] + RT[3 * r + 2] * RP[3 * c + 2];
-        m3_vec(RD, tP, d);
-        for (int q = 0; q < 3; ++q) tD[q] = tT[q] - d[q];
-        for (int i = hi + 1 + tid; i < V; i += 256) {
-            double Ri[9], ti[3], Rn[9];
-            for (int q = 0; q < 9; ++q) Ri[q] = open[(size_t)q * Vs + i];
-            for (int q = 0; q < 3; ++q) ti[q] = open[(size_t)(9 + q) * Vs + i];
-            m3_mul(RD, Ri, Rn);
-            m3_vec(RD, ti, d);
-            for (int q = 0; q < 9; ++q) dst[(size_t)q * Vs + i] = Rn[q];
-            for (int q = 0; q < 3; ++q) dst[(size_t)(9 + q) * Vs + i] = tD[q] + d[q];
+        double R[9], t[3];
+        for (int q = 0; q < 9; ++q) R[q] = C.pose0[(size_t)q * vs + V0 - 1];
+        for (int q = 0; q < 3; ++q) t[q] = C.pose0[(size_t)(9 + q) * vs + V0 - 1];
+        for (int i = V0; i < V0 + n; ++i) {
+            se3_compose_step(R, t, C.chain, C.estride, i);
+            for (int q = 0; q < 9; ++q) C.pose0[(size_t)q * vs + i] = R[q];
+            for (int q = 0; q < 3; ++q) C.pose0[(size_t)(9 + q) * vs + i] = t[q];
         }
     }
+}
+// one edge, carried in the arguments: records and open-loop pose of vertex V0 = k + 1
+template <int DIM>
+__global__ void k_append_odometry_one(RawOdometry r, int k, double scale, ChainPtrs C)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double m[7], inf[21];
+    for (int q = 0; q < 7; ++q) m[q] = r.meas[q];
+    for (int q = 0; q < 21; ++q) inf[q] = r.info[q];
+    append_edge_records<DIM>(m, inf, scale, C, k);
+    append_compose<DIM>(k + 1, 1, C);
+}
+// a burst: one lane per edge k0 .. k0 + n - 1 (meas / info: the engine's pinned staging buffer), then the compose on one lane
+template <int DIM>
+__global__ void k_append_odometry_prep(int n, int k0, const double* meas, const double* info, double scale, ChainPtrs C)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    constexpr int ms = DIM == 2 ? 3 : 7, is = DIM == 2 ? 6 : 21;
+    double m[7], inf[21];
+    for (int q = 0; q < ms; ++q) m[q] = meas[(size_t)ms * j + q];
+    for (int q = 0; q < is; ++q) inf[q] = info[(size_t)is * j + q];
+    append_edge_records<DIM>(m, inf, scale, C, k0 + j);
+}
+template <int DIM>
+__global__ void k_append_odometry_compose(int V0, int n, ChainPtrs C)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    append_compose<DIM>(V0, n, C);
+}
+// The new vertices in the pose states that are alive (the current poses and the pipeline's tentative states, blockIdx.y):
+// D_state (+) open[i], one lane per vertex; a state no accept has written a tail of holds a bit copy of open[i].
+constexpr int kMaxAppendStates = 12;
+struct StateList { double* p[kMaxAppendStates]; };
+template <int NF>
+__global__ void k_append_state_tail(int V0, int n, const double* open, int vs, StateList L)
+{
+    const int i = V0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= V0 + n) return;
+    const size_t Vs = (size_t)vs;
+    double* dst = L.p[blockIdx.y];
+    const double* D = dst + (size_t)NF * Vs;
+    if (D[kPoseTrail - 1] == 0.0) {
+        for (int f = 0; f < NF; ++f) dst[(size_t)f * Vs + i] = open[(size_t)f * Vs + i];
+        return;
+    }
+    if (NF == 5) se2_tail_apply(D, open, Vs, dst, i);
+    else se3_tail_apply(D, open, Vs, dst, i);
 }
 
 static PoseArr pose_arr(double* base, int V)
@@ -2151,8 +2329,8 @@ static int ensure_incremental(ipc_engine* h, const char* who)
     if (h->dim == 3) {
         if (!h->d_cur) {
             h->d_open = h->d_pose0;                   // same [12][V] layout; not owned twice, see ipc_destroy
-            HIPCHK(hipMalloc(&h->d_cur, sizeof(double) * 12 * (size_t)h->V));
-            HIPCHK(copy_d2d_now(h, h->d_cur, h->d_open, sizeof(double) * 12 * (size_t)h->V));
+            HIPCHK(hipMalloc(&h->d_cur, sizeof(double) * (12 * (size_t)h->vcap + kPoseTrail)));
+            if (int rc = reset_current(h)) return rc;
         }
         if (!h->cluster3) {
             h->cluster3 = new ClusterSolver3(); h->cluster3->term_eps = h->term_eps; h->cluster3->allow_damping = h->lm_retry;
@@ -2165,12 +2343,11 @@ static int ensure_incremental(ipc_engine* h, const char* who)
         return IPC_OK;
     }
     if (!h->d_open) {
-        HIPCHK(hipMalloc(&h->d_open, sizeof(double) * 5 * (size_t)h->V));
-        HIPCHK(hipMalloc(&h->d_cur, sizeof(double) * 5 * (size_t)h->V));
-        hipLaunchKernelGGL(k_pose5_init, dim3((h->V + 255) / 256), dim3(256), 0, h->own_stream, h->V, h->d_pose0, h->d_open);
+        HIPCHK(hipMalloc(&h->d_open, sizeof(double) * (5 * (size_t)h->vcap + kPoseTrail)));
+        HIPCHK(hipMalloc(&h->d_cur, sizeof(double) * (5 * (size_t)h->vcap + kPoseTrail)));
+        hipLaunchKernelGGL(k_pose5_init, dim3((h->V + 255) / 256), dim3(256), 0, h->own_stream, h->V, h->d_pose0, h->vcap, h->d_open, h->vcap);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(h->d_cur, h->d_open, sizeof(double) * 5 * (size_t)h->V, hipMemcpyDeviceToDevice, h->own_stream));
-        HIPCHK(hipStreamSynchronize(h->own_stream));
+        if (int rc = reset_current(h)) return rc;
     }
     if (!h->cluster) {
         h->cluster = new ClusterSolver2(); h->cluster->term_eps = h->term_eps; h->cluster->allow_damping = h->lm_retry;
@@ -2205,7 +2382,7 @@ extern "C" int ipc_incremental_reset(ipc_engine_t* h)
     if (!h) return fail(IPC_ERR_ARG, "ipc_incremental_reset: NULL handle");
     if (int rc = ensure_incremental(h, "ipc_incremental_reset")) return rc;
     if (int rc = spec_quiesce(h, true)) return rc;
-    HIPCHK(copy_d2d_now(h, h->d_cur, h->d_open, sizeof(double) * (h->dim == 2 ? 5 : 12) * (size_t)h->V));
+    if (int rc = reset_current(h)) return rc;
     h->cns.clear(); h->cns_dups = false;
     std::fill(h->handed.begin(), h->handed.end(), 0);
     h->porder = h->order;
@@ -2230,13 +2407,16 @@ extern "C" int ipc_incremental_set_state(ipc_engine_t* h, const double* poses, c
     for (size_t i = 0; i < V; ++i)
         for (int f = 0; f < nf; ++f) tmp[(size_t)f * V + i] = poses[(size_t)nf * i + f];
     if (h->dim == 3) {
-        HIPCHK(hipMemcpyAsync(h->d_cur, tmp.data(), sizeof(double) * 12 * V, hipMemcpyHostToDevice, h->own_stream));
+        HIPCHK(hipMemcpy2DAsync(h->d_cur, sizeof(double) * h->vcap, tmp.data(), sizeof(double) * V, sizeof(double) * V, 12, hipMemcpyHostToDevice, h->own_stream));
+        hipLaunchKernelGGL(k_state_D<12>, dim3(1), dim3(64), 0, h->own_stream, h->V, h->vcap, (const double*)h->d_open, h->d_cur);
+        HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(h->own_stream));
     } else {
         double* d_tmp = nullptr;                           // [3][V] -> [5][V] (cos, sin as every pose of the engine carries them)
         HIPCHK(hipMalloc(&d_tmp, sizeof(double) * 3 * V));
         HIPCHK(hipMemcpyAsync(d_tmp, tmp.data(), sizeof(double) * 3 * V, hipMemcpyHostToDevice, h->own_stream));
-        hipLaunchKernelGGL(k_pose5_init, dim3((h->V + 255) / 256), dim3(256), 0, h->own_stream, h->V, d_tmp, h->d_cur);
+        hipLaunchKernelGGL(k_pose5_init, dim3((h->V + 255) / 256), dim3(256), 0, h->own_stream, h->V, d_tmp, h->V, h->d_cur, h->vcap);
+        hipLaunchKernelGGL(k_state_D<5>, dim3(1), dim3(64), 0, h->own_stream, h->V, h->vcap, (const double*)h->d_open, h->d_cur);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(h->own_stream));
         HIPCHK(hipFree(d_tmp));
@@ -2355,11 +2535,11 @@ static int apply_accept(ipc_engine* h, hipStream_t st, double* dst, const double
                         const double* X3, int ld3)
 {
     if (h->dim == 3)
-        hipLaunchKernelGGL(k_apply_accept<12>, dim3(1), dim3(256), 0, st, h->V, lo, hi, parent, X3, ld3, (const double*)h->d_open, dst);
+        hipLaunchKernelGGL(k_apply_accept<12>, dim3(1), dim3(256), 0, st, h->V, h->vcap, lo, hi, parent, X3, ld3, (const double*)h->d_open, dst);
     else if (X2->th - X2->y != X2->y - X2->x || X2->c - X2->th != X2->y - X2->x || X2->s - X2->c != X2->y - X2->x)
         return fail(IPC_ERR_STATE, "apply_accept: the solver's pose arrays are not rows of one block");
     else                                            // (x, y, th, c, s: rows of one block, ClusterSolver2 / PersistSe2::carve)
-        hipLaunchKernelGGL(k_apply_accept<5>, dim3(1), dim3(256), 0, st, h->V, lo, hi, parent, X2->x, (int)(X2->y - X2->x),
+        hipLaunchKernelGGL(k_apply_accept<5>, dim3(1), dim3(256), 0, st, h->V, h->vcap, lo, hi, parent, X2->x, (int)(X2->y - X2->x),
                            (const double*)h->d_open, dst);
     HIPCHK(hipGetLastError());
     return IPC_OK;
@@ -2417,11 +2597,11 @@ static int spec_ensure(ipc_engine* h)
         if (h->dim == 3) {
             sl.s3 = new PersistSolver<PersistSe3>(h->knobs); sl.s3->term_eps = h->term_eps; sl.s3->d_prof = q == 0 ? h->d_prof : nullptr;
             sl.s3->d_abort_word = h->d_abort + q;
-            HIPCHK(sl.s3->reserve(h->V - 1, std::max(256, std::min(h->N + 1, 16384)), 256));
+            HIPCHK(sl.s3->reserve(h->vcap - 1, std::max(256, std::min(h->N + 1, 16384)), 256));
         } else {
             sl.s2 = new PersistSolver<PersistSe2>(h->knobs); sl.s2->term_eps = h->term_eps; sl.s2->d_prof = q == 0 ? h->d_prof : nullptr;
             sl.s2->d_abort_word = h->d_abort + q;
-            HIPCHK(sl.s2->reserve(h->V - 1, std::max(256, std::min(h->N + 1, 16384)), 256));
+            HIPCHK(sl.s2->reserve(h->vcap - 1, std::max(256, std::min(h->N + 1, 16384)), 256));
         }
     }
     if (!h->window_forced) {
@@ -2472,7 +2652,7 @@ static int spec_alloc_state(ipc_engine* h, int& idx)
         h->spec_states.emplace_back();
         idx = (int)h->spec_states.size() - 1;
         ipc_engine::SpecState& n = h->spec_states[idx];
-        HIPCHK(hipMalloc(&n.d_poses, sizeof(double) * (h->dim == 2 ? 5 : 12) * (size_t)h->V));
+        HIPCHK(hipMalloc(&n.d_poses, sizeof(double) * ((h->dim == 2 ? 5 : 12) * (size_t)h->vcap + kPoseTrail)));
         n.owned = true;
         HIPCHK(hipEventCreateWithFlags(&n.ready, hipEventDisableTiming));
     }
@@ -2553,10 +2733,10 @@ static int spec_predict_state(ipc_engine* h, int si, hipStream_t st)
     if (h->cand_event) HIPCHK(hipStreamWaitEvent(st, h->ev_cand, 0));
     S.pred_n = h->N;
     if (h->dim == 3)
-        hipLaunchKernelGGL(k_cand_own_chi2_se3, dim3((h->N + 127) / 128), dim3(128), 0, st, (const double*)S.d_poses, h->V,
+        hipLaunchKernelGGL(k_cand_own_chi2_se3, dim3((h->N + 127) / 128), dim3(128), 0, st, (const double*)S.d_poses, h->vcap,
                            (const double*)h->d_cand, h->cstride, (const int*)h->d_from, (const int*)h->d_to, h->N, S.d_pred);
     else
-        hipLaunchKernelGGL(k_cand_own_chi2_se2, dim3((h->N + 127) / 128), dim3(128), 0, st, (const double*)S.d_poses, h->V,
+        hipLaunchKernelGGL(k_cand_own_chi2_se2, dim3((h->N + 127) / 128), dim3(128), 0, st, (const double*)S.d_poses, h->vcap,
                            (const double*)h->d_cand, h->cstride, (const int*)h->d_from, (const int*)h->d_to, h->N, S.d_pred);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(S.pred_ev, st));
@@ -2596,11 +2776,11 @@ static int spec_launch(ipc_engine* h, int q, int p, int helpers, bool expect_rej
     if (h->dim == 3) sl.s3->economy = expect_reject; else sl.s2->economy = expect_reject;
     if (h->dim == 3) {
         sl.s3->launch_id = sl.launch_id;
-        HIPCHK(sl.s3->launch(sl.st, h->d_chain, h->estride, h->d_cand, h->cstride, S.d_poses, h->V, c.lo, c.hi, c.members,
+        HIPCHK(sl.s3->launch(sl.st, h->d_chain, h->estride, h->d_cand, h->cstride, S.d_poses, h->vcap, c.lo, c.hi, c.members,
                              h->h_from.data(), h->h_to.data(), c.iters));
     } else {
         sl.s2->launch_id = sl.launch_id;
-        HIPCHK(sl.s2->launch(sl.st, h->d_chain, h->estride, h->d_cand, h->cstride, S.d_poses, h->V, c.lo, c.hi, c.members,
+        HIPCHK(sl.s2->launch(sl.st, h->d_chain, h->estride, h->d_cand, h->cstride, S.d_poses, h->vcap, c.lo, c.hi, c.members,
                              h->h_from.data(), h->h_to.data(), c.iters));
     }
     HIPCHK(hipEventRecord(sl.done, sl.st));
@@ -2624,6 +2804,7 @@ static int spec_make_tentative(ipc_engine* h, int p, int q)
     ipc_engine::SpecState& T = h->spec_states[t];
     if (P.has_ready) HIPCHK(hipStreamWaitEvent(sl.st, P.ready, 0));
     else if (!P.owned && h->commit_count) HIPCHK(hipStreamWaitEvent(sl.st, h->ev_commit, 0));
+    if (h->cand_event) HIPCHK(hipStreamWaitEvent(sl.st, h->ev_cand, 0));  // (open-loop poses ipc_append_odometry wrote on own_stream since the solve was launched: the tail reads them)
     if (h->dim == 3) {
         const double* res = sl.s3->result_in_second() ? sl.s3->dev().Xn : sl.s3->dev().X;
         if (int rc = apply_accept(h, sl.st, T.d_poses, P.d_poses, R.lo, R.hi, nullptr, res, sl.s3->ld())) return rc;
@@ -2990,7 +3171,7 @@ static int agreement_check_speculative(ipc_engine* h, int k, int* agrees, ipc_ch
             h->cns = T.cns;
             // the poses everyone outside the pipeline reads
             HIPCHK(hipStreamWaitEvent(h->own_stream, T.ready, 0));
-            HIPCHK(hipMemcpyAsync(h->d_cur, T.d_poses, sizeof(double) * (h->dim == 2 ? 5 : 12) * (size_t)h->V, hipMemcpyDeviceToDevice,
+            HIPCHK(hipMemcpyAsync(h->d_cur, T.d_poses, sizeof(double) * ((h->dim == 2 ? 5 : 12) * (size_t)h->vcap + kPoseTrail), hipMemcpyDeviceToDevice,
                                   h->own_stream));
             HIPCHK(hipEventRecord(h->ev_commit, h->own_stream));
             ++h->commit_count;
@@ -3043,6 +3224,176 @@ extern "C" int ipc_agreement_check(ipc_engine_t* h, int k, int* agrees, ipc_chec
     h->handed[k] = 1;
     *agrees = agree ? 1 : 0;
     fill_info(info, c.lo, c.hi, c.nclu, o);
+    return IPC_OK;
+}
+
+// ---- online mode: the odometry chain grows in place (ipc_append_odometry, ipc_reserve_vertices, ipc_vertex_count) ----
+static ChainPtrs chain_ptrs(const ipc_engine* h)
+{
+    return ChainPtrs{h->d_chain, h->estride, h->d_chain_rec, h->d_chain_blk, h->d_chain1, h->d_pose0, h->dim == 2 ? h->d_open : nullptr, h->vcap};
+}
+
+// The chain outgrew its arrays: new ones for `cap` vertices (a multiple of 64), everything copied over on own_stream.  As
+// grow_candidates: the old arrays are RETIRED, not freed.  Unlike an append within the capacity a growth gives the look-ahead
+// pipeline up (its solves read the chain and the pose states by pointer) and waits for the device; log2 V times over a run,
+// or never after ipc_reserve_vertices.
+static int grow_chain(ipc_engine* h, int cap)
+{
+    if (int rc = spec_quiesce(h, true)) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    const int nf = h->dim == 2 ? (int)F_NFIELDS : (int)G_NFIELDS, ps = h->dim == 2 ? 3 : 12, NF = h->dim == 2 ? 5 : 12;
+    const int E = h->V - 1, ostride = h->estride, ocap = h->vcap, nstride = cap;
+    hipStream_t st = h->own_stream;
+    auto retire = [&](void* q) { if (q) h->retired.push_back(q); };
+    auto regrow = [&](double*& arr, size_t ndoubles, int rows, int ncopy, int opitch, int npitch) -> int {
+        double* n = nullptr;
+        HIPCHK(hipMalloc(&n, sizeof(double) * ndoubles));
+        HIPCHK(hipMemsetAsync(n, 0, sizeof(double) * ndoubles, st));
+        if (ncopy > 0)
+            HIPCHK(hipMemcpy2DAsync(n, sizeof(double) * npitch, arr, sizeof(double) * opitch, sizeof(double) * ncopy, rows, hipMemcpyDeviceToDevice, st));
+        retire(arr);
+        arr = n;
+        return IPC_OK;
+    };
+    if (int rc = regrow(h->d_chain, nf * (size_t)nstride + 64, nf, E, ostride, nstride)) return rc;
+    if (h->d_chain1) { if (int rc = regrow(h->d_chain1, nf * (size_t)nstride + 64, nf, E, ostride, nstride)) return rc; }
+    if (int rc = regrow(h->d_chain_rec, (size_t)nf * (nstride + 64), 1, E * nf, E * nf, E * nf)) return rc;
+    if (h->dim == 3) {
+        const size_t blk = (size_t)kSe3BlkPairs * 64 * 2;                 // doubles per block of 64 edges
+        double* b = reinterpret_cast<double*>(h->d_chain_blk);
+        const int nold = (E + 63) / 64;
+        if (int rc = regrow(b, blk * ((size_t)nstride / 64 + 2), 1, (int)(blk * nold), (int)(blk * nold), (int)(blk * nold))) return rc;
+        h->d_chain_blk = reinterpret_cast<double2*>(b);
+    }
+    const bool alias = h->d_open == h->d_pose0;                           // (SE3: one array)
+    if (int rc = regrow(h->d_pose0, ps * (size_t)cap, ps, h->V, ocap, cap)) return rc;
+    if (alias) h->d_open = h->d_pose0;
+    else if (h->d_open) { if (int rc = regrow(h->d_open, 5 * (size_t)cap + kPoseTrail, 5, h->V, ocap, cap)) return rc; }
+    double* old_cur = h->d_cur;
+    if (h->d_cur) {
+        if (int rc = regrow(h->d_cur, NF * (size_t)cap + kPoseTrail, NF, h->V, ocap, cap)) return rc;
+        HIPCHK(hipMemcpyAsync(h->d_cur + NF * (size_t)cap, old_cur + NF * (size_t)ocap, sizeof(double) * kPoseTrail, hipMemcpyDeviceToDevice, st));
+    }
+    // the pipeline's pose states (none is alive after the quiesce: their contents go) and its workspaces, sized by the chain
+    for (auto& S : h->spec_states) {
+        if (!S.owned) { S.d_poses = h->d_cur; continue; }
+        retire(S.d_poses);
+        S.d_poses = nullptr;
+        HIPCHK(hipMalloc(&S.d_poses, sizeof(double) * (NF * (size_t)cap + kPoseTrail)));
+    }
+    for (auto& sl : h->slots) {
+        if (sl.s3) HIPCHK(sl.s3->reserve(cap - 1, std::max(256, std::min(h->N + 1, 16384)), 256));
+        if (sl.s2) HIPCHK(sl.s2->reserve(cap - 1, std::max(256, std::min(h->N + 1, 16384)), 256));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    h->estride = nstride; h->vcap = cap;
+    ++h->chain_growths;
+    return IPC_OK;
+}
+
+extern "C" int ipc_vertex_count(ipc_engine_t* h, int* n_vertices)
+{
+    if (!h || !n_vertices) return fail(IPC_ERR_ARG, "ipc_vertex_count: NULL argument");
+    *n_vertices = h->V;
+    return IPC_OK;
+}
+
+extern "C" int ipc_reserve_vertices(ipc_engine_t* h, int capacity)
+{
+    if (!h) return fail(IPC_ERR_ARG, "ipc_reserve_vertices: NULL handle");
+    if (capacity > 0x7fffffff - 128) return fail(IPC_ERR_ARG, "ipc_reserve_vertices: a capacity of %d vertices overflows int", capacity);
+    if (capacity <= h->vcap && capacity - 1 <= h->estride) return IPC_OK;          // (smaller than what is there: nothing to do)
+    HIPCHK(hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> run_lk(device_pipeline(h->device).run_mu);
+    return grow_chain(h, (capacity + 63) & ~63);
+}
+
+// n_edges more odometry edges V-1 -> V, V -> V+1, ... (the chain the reference's constructor takes whole, src/consensus.cpp:13-23):
+// records in every copy of the chain (robustifyVoters' scaling, src/consensus_utils.cpp:124-130), the open-loop poses of the new
+// vertices (propagateGuess resumed, src/consensus_utils.cpp:99-116) and their poses in every pose state that is alive.  Within
+// the capacity: kernels on own_stream and an event -- no allocation, no hipFree, no host synchronisation (one edge; a burst
+// waits for the kernel that read the staging buffer of the burst before), the solves in flight go on (none of them reads a
+// vertex >= V), the cached matrix-mode plan stays (the existing cells do not change).
+extern "C" int ipc_append_odometry(ipc_engine_t* h, int n_edges, const double* meas, const double* info)
+{
+    if (n_edges < 1) return fail(IPC_ERR_ARG, "ipc_append_odometry: n_edges must be >= 1, got %d", n_edges);
+    if (!h) return fail(IPC_ERR_ARG, "ipc_append_odometry: NULL handle");
+    if (!meas || !info) return fail(IPC_ERR_ARG, "ipc_append_odometry: NULL array");
+    if (n_edges > 0x7fffffff - 128 - h->V) return fail(IPC_ERR_ARG, "ipc_append_odometry: %d + %d vertices overflow int", h->V, n_edges);
+    HIPCHK(hipSetDevice(h->device));
+    std::lock_guard<std::recursive_mutex> run_lk(device_pipeline(h->device).run_mu);
+    const int ms = h->dim == 2 ? 3 : 7, is = h->dim == 2 ? 6 : 21, NF = h->dim == 2 ? 5 : 12;
+    const int V0 = h->V, need = V0 + n_edges;
+    if (need > h->vcap || need - 1 > h->estride) {
+        long long cap = std::max(64LL, (2LL * h->vcap + 63) & ~63LL);                  // (twice what is there, in multiples of 64)
+        while (cap < need) cap *= 2;
+        if (cap > 0x7fffffff - 128) return fail(IPC_ERR_ARG, "ipc_append_odometry: a capacity of %lld vertices overflows int", cap);
+        if (int rc = grow_chain(h, (int)cap)) return rc;
+    }
+    hipStream_t st = h->own_stream;
+    if (!h->ev_cand) HIPCHK(hipEventCreateWithFlags(&h->ev_cand, hipEventDisableTiming));
+    const ChainPtrs C = chain_ptrs(h);
+    const double scale = h->prm.s_factor;
+    if (n_edges == 1) {
+        RawOdometry r{};
+        for (int q = 0; q < ms; ++q) r.meas[q] = meas[q];
+        for (int q = 0; q < is; ++q) r.info[q] = info[q];
+        if (h->dim == 2) hipLaunchKernelGGL(k_append_odometry_one<2>, dim3(1), dim3(64), 0, st, r, V0 - 1, scale, C);
+        else hipLaunchKernelGGL(k_append_odometry_one<3>, dim3(1), dim3(64), 0, st, r, V0 - 1, scale, C);
+    } else {
+        const size_t nd = (size_t)(ms + is) * n_edges;
+        if (h->stage_used) HIPCHK(hipEventSynchronize(h->ev_stage));       // (the kernel of the burst before still reads the buffer)
+        if (nd > h->stage_cap) {
+            if (h->h_stage) HIPCHK(hipHostFree(h->h_stage));
+            h->h_stage = nullptr; h->stage_cap = 0;
+            const size_t want = std::max(nd, (size_t)(ms + is) * 1024);
+            HIPCHK(hipHostMalloc(&h->h_stage, sizeof(double) * want, hipHostMallocMapped));
+            HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_stage), h->h_stage, 0));
+            h->stage_cap = want;
+        }
+        if (!h->ev_stage) HIPCHK(hipEventCreateWithFlags(&h->ev_stage, hipEventDisableTiming));
+        std::memcpy(h->h_stage, meas, sizeof(double) * ms * n_edges);
+        std::memcpy(h->h_stage + (size_t)ms * n_edges, info, sizeof(double) * is * n_edges);
+        const double* dm = h->d_stage;
+        const double* di = h->d_stage + (size_t)ms * n_edges;
+        if (h->dim == 2) {
+            hipLaunchKernelGGL(k_append_odometry_prep<2>, dim3((n_edges + 63) / 64), dim3(64), 0, st, n_edges, V0 - 1, dm, di, scale, C);
+            hipLaunchKernelGGL(k_append_odometry_compose<2>, dim3(1), dim3(64), 0, st, V0, n_edges, C);
+        } else {
+            hipLaunchKernelGGL(k_append_odometry_prep<3>, dim3((n_edges + 63) / 64), dim3(64), 0, st, n_edges, V0 - 1, dm, di, scale, C);
+            hipLaunchKernelGGL(k_append_odometry_compose<3>, dim3(1), dim3(64), 0, st, V0, n_edges, C);
+        }
+        HIPCHK(hipEventRecord(h->ev_stage, st));
+        h->stage_used = true;
+    }
+    HIPCHK(hipGetLastError());
+    // the new vertices in the current poses and in every tentative state of the pipeline (own_stream is the stream of the
+    // commits; a tentative state's poses were written on the stream of the solve that made it)
+    if (h->d_cur) {
+        StateList L{};
+        int ns = 0;
+        auto flush = [&]() -> int {
+            if (!ns) return IPC_OK;
+            if (NF == 5) hipLaunchKernelGGL(k_append_state_tail<5>, dim3((n_edges + 63) / 64, ns), dim3(64), 0, st, V0, n_edges, (const double*)h->d_open, h->vcap, L);
+            else hipLaunchKernelGGL(k_append_state_tail<12>, dim3((n_edges + 63) / 64, ns), dim3(64), 0, st, V0, n_edges, (const double*)h->d_open, h->vcap, L);
+            HIPCHK(hipGetLastError());
+            ns = 0;
+            return IPC_OK;
+        };
+        L.p[ns++] = h->d_cur;
+        for (auto& S : h->spec_states) {
+            if (!S.live || !S.owned) continue;
+            if (S.has_ready) HIPCHK(hipStreamWaitEvent(st, S.ready, 0));
+            L.p[ns++] = S.d_poses;
+            if (ns == kMaxAppendStates) { if (int rc = flush()) return rc; }
+        }
+        if (int rc = flush()) return rc;
+    }
+    HIPCHK(hipEventRecord(h->ev_cand, st));                                // (what every stream of the engine waits for before its next launch)
+    h->cand_event = true;
+    h->h_odom_meas.insert(h->h_odom_meas.end(), meas, meas + (size_t)ms * n_edges);
+    h->h_odom_info.insert(h->h_odom_info.end(), info, info + (size_t)is * n_edges);
+    h->V = need;
     return IPC_OK;
 }
 
@@ -3126,8 +3477,9 @@ extern "C" int ipc_current_poses(ipc_engine_t* h, double* poses_out)
     if (!h || !poses_out) return fail(IPC_ERR_ARG, "ipc_current_poses: NULL argument");
     if (int rc = ensure_incremental(h, "ipc_current_poses")) return rc;
     if (int rc = spec_quiesce(h, false)) return rc;
-    if (h->dim == 3) return download_poses3(h, h->d_cur, h->V, h->V, poses_out);
-    return download_poses(h, pose_arr(h->d_cur, h->V), h->V, poses_out);
+    HIPCHK(hipStreamSynchronize(h->own_stream));               // (vertices ipc_append_odometry is still writing)
+    if (h->dim == 3) return download_poses3(h, h->d_cur, h->vcap, h->V, poses_out);
+    return download_poses(h, pose_arr(h->d_cur, h->vcap), h->V, poses_out);
 }
 
 extern "C" int ipc_final_optimize(ipc_engine_t* h, const uint8_t* accepted, int iterations, double* poses_out,
@@ -3165,8 +3517,9 @@ extern "C" int ipc_final_optimize(ipc_engine_t* h, const uint8_t* accepted, int 
         // pure odometry: the open-loop guess already has zero error, optimize() leaves it alone
         ClusterOut o;
         fill_info(info, 0, h->V - 1, 0, o);
-        if (poses_out && h->dim == 3) return download_poses3(h, h->d_open, h->V, h->V, poses_out);
-        if (poses_out) return download_poses(h, pose_arr(h->d_open, h->V), h->V, poses_out);
+        HIPCHK(hipStreamSynchronize(h->own_stream));
+        if (poses_out && h->dim == 3) return download_poses3(h, h->d_open, h->vcap, h->V, poses_out);
+        if (poses_out) return download_poses(h, pose_arr(h->d_open, h->vcap), h->V, poses_out);
         return IPC_OK;
     }
     ClusterOut o;

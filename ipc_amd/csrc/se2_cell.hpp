@@ -56,7 +56,7 @@ struct Se2View {
     const double* chain;      // [F_NFIELDS][estride], index = edge k (joins pose k -> k+1)
     int estride;
     const double* chain_rec;  // the same values record-major: [edge][F_NFIELDS] (+ zero padding)
-    const double* pose0;      // [3][V] open-loop poses x, y, theta
+    const double* pose0;      // [3][VS] open-loop poses x, y, theta (V of them)
     int V;
     const double* cand;       // [F_NFIELDS][cstride] per loop candidate
     int cstride;
@@ -76,6 +76,7 @@ struct Se2View {
     // (slow crawls along a flat valley, up to the iteration cap) runs g2o's loop unchanged: cutting those
     // short would move their per-edge chi2 by ~5e-5.
     double term_eps;
+    int VS;                   // stride of pose0's rows (>= V: the chain grows in place, ipc_append_odometry)
 };
 
 struct SolveParams {
@@ -344,8 +345,8 @@ __device__ void se2_solve_cell(const Se2View& P, int lo_abs, int L, const int (&
     int ek[M];                                       // absolute edge index of the slot
     Pose2 gauge;
     gauge.x = P.pose0[lo_abs];
-    gauge.y = P.pose0[(size_t)P.V + lo_abs];
-    gauge.th = P.pose0[(size_t)2 * P.V + lo_abs];
+    gauge.y = P.pose0[(size_t)P.VS + lo_abs];
+    gauge.th = P.pose0[(size_t)2 * P.VS + lo_abs];
     sincos_pi(gauge.th, gauge.s, gauge.c);
 #pragma unroll
     for (int s = 0; s < M; ++s) {
@@ -354,8 +355,8 @@ __device__ void se2_solve_cell(const Se2View& P, int lo_abs, int L, const int (&
         ek[s] = valid[s] ? lo_abs + j - 1 : lo_abs;
         const int ja = valid[s] ? lo_abs + j : lo_abs;
         Xn[s].x = P.pose0[ja];
-        Xn[s].y = P.pose0[(size_t)P.V + ja];
-        Xn[s].th = P.pose0[(size_t)2 * P.V + ja];
+        Xn[s].y = P.pose0[(size_t)P.VS + ja];
+        Xn[s].th = P.pose0[(size_t)2 * P.VS + ja];
         sincos_pi(Xn[s].th, Xn[s].s, Xn[s].c);
         X[s] = Xn[s];
         hx[s] = hy[s] = hth[s] = 0.0;

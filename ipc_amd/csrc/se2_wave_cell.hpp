@@ -294,16 +294,16 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
     double hx[M], hy[M], hth[M];
     Pose2 gauge;
     gauge.x = P.pose0[lo_abs];
-    gauge.y = P.pose0[(size_t)P.V + lo_abs];
-    gauge.th = P.pose0[(size_t)2 * P.V + lo_abs];
+    gauge.y = P.pose0[(size_t)P.VS + lo_abs];
+    gauge.th = P.pose0[(size_t)2 * P.VS + lo_abs];
     sincos_pi(gauge.th, gauge.s, gauge.c);
 #pragma unroll
     for (int s = 0; s < M; ++s) {
         const int j = j0 + s;
         const int ja = j <= L ? lo_abs + j : lo_abs;
         X[s].x = P.pose0[ja];
-        X[s].y = P.pose0[(size_t)P.V + ja];
-        X[s].th = P.pose0[(size_t)2 * P.V + ja];
+        X[s].y = P.pose0[(size_t)P.VS + ja];
+        X[s].th = P.pose0[(size_t)2 * P.VS + ja];
         sincos_pi(X[s].th, X[s].s, X[s].c);
         if (KEEP_E) ex[s] = ey[s] = eth[s] = 0.0;
         bx[s] = by[s] = bth[s] = 0.0;

@@ -34,7 +34,7 @@ struct Se3View {
     int estride;
     const double* chain_rec;  // the same values record-major: [edge][G_NFIELDS]
     const double2* chain_blk; // the same values in blocks of 64 edges: [block][kSe3BlkPairs][64] double2 (se3_lds_cell.hpp)
-    const double* pose0;      // [12][V] open-loop poses: R row-major (9), t (3)
+    const double* pose0;      // [12][VS] open-loop poses (V of them): R row-major (9), t (3)
     int V;
     const double* cand;       // [G_NFIELDS][cstride]
     int cstride;
@@ -42,6 +42,7 @@ struct Se3View {
     const int* cand_to;
     double term_eps;          // convergence shortcut of the trial loop, see Se2View::term_eps
     double* dbg;              // debug side channel (NULL in production)
+    int VS;                   // stride of pose0's rows (>= V: the chain grows in place, ipc_append_odometry)
 };
 
 struct Pose3 { double R[9]; double t[3]; };
@@ -346,9 +347,9 @@ __device__ void se3_solve_cell(const Se3View& P, int lo_abs, int L, const int (&
     unsigned eoff[M];
     Pose3 gauge;
 #pragma unroll
-    for (int k = 0; k < 9; ++k) gauge.R[k] = P.pose0[(size_t)k * P.V + lo_abs];
+    for (int k = 0; k < 9; ++k) gauge.R[k] = P.pose0[(size_t)k * P.VS + lo_abs];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) gauge.t[k] = P.pose0[(size_t)(9 + k) * P.V + lo_abs];
+    for (int k = 0; k < 3; ++k) gauge.t[k] = P.pose0[(size_t)(9 + k) * P.VS + lo_abs];
 #pragma unroll
     for (int s = 0; s < M; ++s) {
         const int j = jbase + s * 64;
@@ -356,9 +357,9 @@ __device__ void se3_solve_cell(const Se3View& P, int lo_abs, int L, const int (&
         eoff[s] = (unsigned)(valid[s] ? lo_abs + j - 1 : lo_abs) * (unsigned)(G_NFIELDS * 8);   // byte offset of the edge record
         const int ja = valid[s] ? lo_abs + j : lo_abs;
 #pragma unroll
-        for (int k = 0; k < 9; ++k) X[s].R[k] = P.pose0[(size_t)k * P.V + ja];
+        for (int k = 0; k < 9; ++k) X[s].R[k] = P.pose0[(size_t)k * P.VS + ja];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) X[s].t[k] = P.pose0[(size_t)(9 + k) * P.V + ja];
+        for (int k = 0; k < 3; ++k) X[s].t[k] = P.pose0[(size_t)(9 + k) * P.VS + ja];
         Xn[s] = X[s];
 #pragma unroll
         for (int k = 0; k < 6; ++k) { e[s][k] = b[s][k] = h[s][k] = 0.0; }

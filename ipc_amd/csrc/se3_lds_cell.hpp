@@ -147,9 +147,9 @@ __device__ __forceinline__ void se3_lds_solve(const Se3View& P, int lo_abs, int 
     // ---------------- poses -> LDS (idle slots hold a copy of the gauge) ----------------
     Pose3 gauge;
 #pragma unroll
-    for (int k = 0; k < 9; ++k) gauge.R[k] = P.pose0[(size_t)k * P.V + lo_abs];
+    for (int k = 0; k < 9; ++k) gauge.R[k] = P.pose0[(size_t)k * P.VS + lo_abs];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) gauge.t[k] = P.pose0[(size_t)(9 + k) * P.V + lo_abs];
+    for (int k = 0; k < 3; ++k) gauge.t[k] = P.pose0[(size_t)(9 + k) * P.VS + lo_abs];
     auto st_pose = [&](int p, const PoseQ& y) {
         sh.q01[p] = make_double2(y.q[0], y.q[1]);
         sh.q23[p] = make_double2(y.q[2], y.q[3]);
@@ -174,10 +174,10 @@ __device__ __forceinline__ void se3_lds_solve(const Se3View& P, int lo_abs, int 
             if (j <= L) {
                 double R[9];
 #pragma unroll
-                for (int k = 0; k < 9; ++k) R[k] = P.pose0[(size_t)k * P.V + lo_abs + j];
+                for (int k = 0; k < 9; ++k) R[k] = P.pose0[(size_t)k * P.VS + lo_abs + j];
                 quat_from_R(R, y.q);
 #pragma unroll
-                for (int k = 0; k < 3; ++k) y.t[k] = P.pose0[(size_t)(9 + k) * P.V + lo_abs + j];
+                for (int k = 0; k < 3; ++k) y.t[k] = P.pose0[(size_t)(9 + k) * P.VS + lo_abs + j];
             }
             st_pose(j, y);
         }
