@@ -221,7 +221,46 @@ int ipc_run_set_only(ipc_engine_t* h, uint8_t* accepted_out, int* solved_cells_o
  * (78 MB for C5: ~5 ms instead of < 1 ms).  Engines that share a device (tests) copy device to device. */
 int ipc_run_sharded(ipc_engine_t** engines, int n_engines, uint64_t* bits_out, uint8_t* accepted_out);
 
-/* Diagnostics of the last ipc_solve_rows(): number of solved cells, and their records. */
+/* ---- online matrix mode: the matrix stays on the device, an update solves only the cells of new candidates -----------------
+ * The matrix form is this project's re-formulation of src/consensus.cpp:43-75,124-171 (agreementCheck +
+ * computeIndependentSubgraph).  A cell (i, j) reads the chain records and open-loop poses of [min lo, max hi], the two candidate
+ * records and the parameters -- no other candidate, not N, no vertex appended later (ipc_append_odometry never rewrites an
+ * existing pose).  So the matrix over candidates 0..N-1 is the matrix over 0..M-1 plus the cells of the columns M..N-1, and the
+ * greedy set (processing order (max id, index)) of a prefix of the order is the whole run's set restricted to it.
+ *
+ * ipc_run_online: with M = the number of candidates the engine's online matrix covers (ipc_online_covered), solves every cell
+ * (i, j >= i) with j >= M and no other, extends the stored symmetric matrix by the new rows and columns, updates the accepted
+ * set and sets M = N.  M = 0: a whole solve.  M = N: nothing is solved, the stored result is returned.  Outputs as ipc_run,
+ * sized by the N of the moment, any may be NULL: bits_out [N][ceil(N/64)] (78 MB at N = 25 000: an online caller passes NULL and
+ * reads accepted_out [N]).  Bit for bit the outputs of ipc_run on the same list.  The greedy continues from the stored accepted
+ * mask when every new candidate sits behind every covered one in the processing order (a candidate that arrives with the newest
+ * vertex does), otherwise it is rerun from the start over the stored matrix; report->set_max_resumed says which.  The N limit
+ * of ipc_set_max applies (IPC_ERR_LIMIT).  One engine, world 1.
+ * The call enters matrix mode like every other matrix call (the faithful pipeline's solves in flight are given up) and shares the
+ * cell buffers of ipc_solve_rows: afterwards ipc_cell_count, ipc_cell_info and ipc_solve_report describe the cells of THIS call
+ * (none after a call with M = N), and the next ipc_solve_rows / ipc_run plans its lists again.  ipc_run, ipc_run_set_only,
+ * ipc_solve_rows and ipc_run_sharded neither read nor change the online matrix.
+ * Storage: solved upper-triangle bits and the symmetric matrix as [capacity][capacity / 64] words, capacity a multiple of 64 that
+ * doubles (the old arrays are retired, not freed, as ipc_append_candidate's are); within the capacity an update allocates and
+ * frees nothing.  ipc_reserve_candidates gives room for `capacity` candidates up front, in the candidate arrays and in the online
+ * matrix (no-op below the current capacity; the counterpart of ipc_reserve_vertices; kept across ipc_set_candidates).  It may be
+ * called on a list in use: the records move on the engine's stream and the next matrix call plans its lists again.  The matrix
+ * is quadratic in the capacity (2 x capacity^2 / 8 bytes): a capacity the device has no room for is IPC_ERR_LIMIT before anything
+ * is allocated (so is the growth inside ipc_run_online), and beyond the N limit above only the candidate arrays are reserved.
+ * ipc_online_reset forgets the matrix (M = 0); ipc_set_candidates does so implicitly, as for the incremental state. */
+typedef struct {
+    int covered_before, covered_after;   /* M before and after the call (after: N)                                   */
+    int cells;                           /* cells solved by this call                                                */
+    int long_cells, literal_cells, damped_cells;   /* as in ipc_solve_report_t, for this call                        */
+    int set_max_resumed;                 /* 1: the greedy continued from the stored mask, 0: rerun from the start (or nothing to do) */
+    int grew;                            /* 1: the matrix storage was re-laid out to a larger capacity               */
+} ipc_online_report_t;
+int ipc_run_online(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accepted_out, ipc_online_report_t* report);
+int ipc_online_covered(ipc_engine_t* h, int* m);
+int ipc_online_reset(ipc_engine_t* h);
+int ipc_reserve_candidates(ipc_engine_t* h, int capacity);
+
+/* Diagnostics of the last ipc_solve_rows() or ipc_run_online(): number of solved cells, and their records. */
 int ipc_cell_count(ipc_engine_t* h, int* n_cells);
 int ipc_cell_info(ipc_engine_t* h, ipc_cell_info_t* out, int capacity);
 

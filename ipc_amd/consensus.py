@@ -127,6 +127,35 @@ class IPC:
         self._max_consensus_set = order[acc[order] == 1]
         return acc, n.value
 
+    # ---- online matrix mode: the matrix stays on the device, an update solves the new columns ----
+    def run_online(self, want_bits=False):
+        """ipc_run_online: solve the cells of the candidates appended since the last call, extend the stored matrix and the
+        accepted set.  Returns (accepted [N] uint8, report dict), or (bits [N, words] uint64, accepted, report) with
+        want_bits; the results are those of run() on the same list."""
+        acc = np.zeros(self.N, dtype=np.uint8)
+        bits = np.zeros((self.N, self.words), dtype=np.uint64) if want_bits else None
+        r = capi.OnlineReport()
+        capi.check(self.lib.ipc_run_online(self.h, _p(bits) if want_bits else None, _p(acc), C.byref(r)))
+        order = self.candidate_order()
+        self._max_consensus_set = order[acc[order] == 1]
+        report = {k: getattr(r, k) for k, _ in capi.OnlineReport._fields_}
+        return (bits, acc, report) if want_bits else (acc, report)
+
+    @property
+    def online_covered(self):
+        """How many candidates the online matrix covers (ipc_online_covered)."""
+        m = C.c_int(0)
+        capi.check(self.lib.ipc_online_covered(self.h, C.byref(m)))
+        return m.value
+
+    def online_reset(self):
+        """Forget the online matrix (ipc_online_reset): the next run_online solves every cell."""
+        capi.check(self.lib.ipc_online_reset(self.h))
+
+    def reserve_candidates(self, n):
+        """Room for n candidates up front, in the candidate arrays and the online matrix (ipc_reserve_candidates)."""
+        capi.check(self.lib.ipc_reserve_candidates(self.h, int(n)))
+
     def consistency_matrix(self):
         bits, _ = self.run()
         return unpack_bits(bits, self.N)

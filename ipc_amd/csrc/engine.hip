@@ -321,6 +321,46 @@ __global__ void k_plan(int N, const int* lo, const int* hi, const int* rowperm, 
     }
 }
 
+// The cell lists of the columns M .. N-1 (ipc_run_online): thread grid (row i) x (new candidate j), a cell exists for i <= j by
+// the rule of k_plan -- the diagonal cell in the one-loop slot of bin_of(hi - lo), a pair cell only where the intervals overlap
+// with positive length, in the two-loop slot of the union's bin.  O(N (N - M)) compares.  Same counter layout and the same
+// wave-aggregated append as k_plan (one atomic per wave and slot present, kPlanSub sub-counters per slot: here the block and the
+// column pick the sub-counter, the same one in the count and in the fill pass); the lists are used once, so their order is free.
+__global__ void k_plan_delta(int N, int M, const int* lo, const int* hi, BinCaps bc, unsigned* counters,
+                             const unsigned* offsets, int2* cells, int fill)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;          // this thread's row, its interval read once
+    const int loi = i < N ? lo[i] : 0, hii = i < N ? hi[i] : 0;
+    const int lane = threadIdx.x & 63;
+    for (int j = M + blockIdx.y; j < N; j += gridDim.y) {
+        if ((int)(blockIdx.x * blockDim.x) > j) continue;         // this block's rows all lie behind column j
+        const int loj = lo[j], hij = hi[j];                       // (uniform: scalar loads)
+        int slot = -1;
+        if (i <= j) {
+            if (i == j) slot = bin_of(bc, hii - loi);
+            else if (min(hii, hij) - max(loi, loj) > 0)           // reference src/consensus.cpp:157-159
+                slot = (kMaxBins + 1) + bin_of(bc, max(hii, hij) - min(loi, loj));
+        }
+        const int sub = (blockIdx.x + j) & (kPlanSub - 1);
+        unsigned long long todo = __ballot(slot >= 0);
+        while (todo) {
+            const int leader = __ffsll((long long)todo) - 1;
+            const int sl = __shfl(slot, leader, 64);
+            const unsigned long long same = __ballot(slot == sl);
+            const int nsame = __popcll(same);
+            unsigned base = 0;
+            const int sc = sl * kPlanSub + sub;
+            if (lane == leader) base = atomicAdd(&counters[sc], (unsigned)nsame);
+            base = __shfl(base, leader, 64);
+            if (slot == sl && fill) {
+                const int rnk = __popcll(same & ((1ull << lane) - 1ull));
+                cells[offsets[sc] + base + rnk] = make_int2(i, j);
+            }
+            todo &= ~same;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // results -> bits
 // ------------------------------------------------------------------------------------------
@@ -333,6 +373,18 @@ __global__ void k_scatter_bits(int ncells, const int2* cells, const double* chi,
     const double th = cc.x == cc.y ? fast_th : slow_th;
     const bool ok = !(chi[c] > th);                 // consensus_utils.cpp:18 (NaN agrees, as there)
     if (ok) atomicOr(&upper[(size_t)(slot[cc.x] % rpr) * words + (cc.y >> 6)], 1ull << (cc.y & 63));
+}
+
+// The online matrix's rows: identity row map, capacity stride (words per stored row).
+__global__ void k_scatter_bits_delta(int ncells, const int2* cells, const double* chi, double fast_th, double slow_th,
+                                     int stride, unsigned long long* upper)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= ncells) return;
+    const int2 cc = cells[c];
+    const double th = cc.x == cc.y ? fast_th : slow_th;
+    const bool ok = !(chi[c] > th);                 // consensus_utils.cpp:18 (NaN agrees, as there)
+    if (ok) atomicOr(&upper[(size_t)cc.x * stride + (cc.y >> 6)], 1ull << (cc.y & 63));
 }
 
 // Symmetric N x N bit matrix from the gathered upper-triangle rows (row a at gathered row slot[a] = owner * rpr + its
@@ -376,14 +428,69 @@ __global__ __launch_bounds__(256) void k_assemble(int N, int words, const int* s
     }
 }
 
+// The online matrix grows from M to N candidates: the rows M .. N-1 are written in full, of the rows below M only the words
+// M >> 6 .. (N - 1) >> 6 -- and of the boundary word M >> 6 (M not a multiple of 64) only the bits of the columns >= M: what an
+// old row holds at an old column is neither recomputed nor written.  The rule, the one compare per lane and the ballot are
+// those of k_assemble; `upper` and `bits` are [.][stride] words with the identity row map.  A block owns word w: a word with
+// new columns visits every row tile, any other word the tiles that hold new rows.
+__global__ __launch_bounds__(256) void k_assemble_delta(int N, int M, int stride, const int* lo, const int* hi,
+                                                        const unsigned long long* upper, unsigned long long* bits)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int w = blockIdx.x;
+    auto U = [&](int a, int c) -> unsigned {        // a <= c
+        const unsigned long long word = upper[(size_t)a * stride + (c >> 6)];
+        return (unsigned)((word >> (c & 63)) & 1ull);
+    };
+    const int w0 = M >> 6, w1 = (N - 1) >> 6;       // words with new columns = row tiles with new rows
+    const bool neww = w >= w0;
+    const unsigned long long keep = (w == w0 && (M & 63)) ? (1ull << (M & 63)) - 1ull : 0ull;   // old columns of the boundary word
+    const int j = w * 64 + lane;
+    const bool vj = j < N;
+    const int loj = vj ? lo[j] : 0, hij = vj ? hi[j] : 0;
+    const unsigned long long Dword = __ballot(vj && U(j, j));
+    for (int rb = (neww ? 0 : w0) + blockIdx.y * 4 + wave; rb <= w1; rb += gridDim.y * 4) {
+        const int ir = rb * 64 + lane;                 // this lane's row of the tile
+        const bool vr = ir < N;
+        const int lor = vr ? lo[ir] : 0, hir = vr ? hi[ir] : 0;
+        const unsigned long long dmask = __ballot(vr && U(ir, ir));
+        const int nrows = min(64, N - rb * 64);
+        unsigned long long mine = 0ull;
+        for (int r = 0; r < nrows; ++r) {
+            const int i = rb * 64 + r;
+            if (i < M && !neww) continue;              // an old row, a word of old columns: stays
+            const int loi = __builtin_amdgcn_readlane(lor, r), hii = __builtin_amdgcn_readlane(hir, r);
+            unsigned long long word = ((dmask >> r) & 1ull) ? Dword : 0ull;
+            const bool ov = vj && j != i && (min(hii, hij) - max(loi, loj) > 0);
+            const unsigned long long ovmask = __ballot(ov);
+            if (ovmask) {
+                const bool bit = ov && U(min(i, j), max(i, j));
+                word = (word & ~ovmask) | __ballot(bit);
+            }
+            if (lane == r) mine = word;
+        }
+        if (vr) {
+            unsigned long long* dst = bits + (size_t)ir * stride + w;
+            if (ir >= M) *dst = mine;
+            else if (neww) *dst = keep ? ((*dst & keep) | (mine & ~keep)) : mine;
+        }
+    }
+}
+
 // Greedy set-max: candidates in processing order, 64 per round (four per wave -- 32 / two until round 5: a round is two
 // trips to memory whatever it holds, and at N = 25 000 the 160 rounds were 1.3 ms that no rank of an 8-GPU run can shed;
 // the rows of a wave's candidates are requested together,
 // a round is a memory round trip).  Candidates whose own cell failed can never join, so the order list is first
 // compacted to those with a set diagonal bit (order preserved).  Within a round the candidates are taken in order: one
 // joins if its row covers the set as it stood before the round AND every member of the round taken before it.
-__global__ __launch_bounds__(1024) void k_set_max(int N, int words, const int* order,
-                                                  const unsigned long long* bits, unsigned char* accepted, int* live)
+// `stride` = words per stored row (ipc_set_max: words; the online matrix: its capacity stride).  Resuming (ipc_run_online):
+// with `mask` / `nlive_io` given the accepted mask and the length of the live list are left in global memory at the end, and a
+// call with first > 0 starts from them -- the candidates at the positions first .. N-1 of the order are compacted behind the
+// stored live list and tested, in order, against the stored set and against each other, exactly as the rounds of a whole run
+// reach them (the greedy's verdict on a candidate reads the verdicts in front of it only).
+__global__ __launch_bounds__(1024) void k_set_max(int N, int words, int stride, const int* order,
+                                                  const unsigned long long* bits, unsigned char* accepted, int* live,
+                                                  int first = 0, unsigned long long* mask = nullptr, int* nlive_io = nullptr)
 {
     constexpr int CPW = 4, RC = 16 * CPW;           // candidates per wave / per round
     extern __shared__ unsigned long long acc[];     // [words] accepted mask
@@ -393,14 +500,16 @@ __global__ __launch_bounds__(1024) void k_set_max(int N, int words, const int* o
     __shared__ int wcount[16];
     __shared__ int nlive_s;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    for (int w = tid; w < words; w += blockDim.x) acc[w] = 0ull;
-    for (int k = tid; k < N; k += blockDim.x) accepted[k] = 0;
-    if (tid == 0) nlive_s = 0;
+    for (int w = tid; w < words; w += blockDim.x) acc[w] = first ? mask[w] : 0ull;
+    if (first) { for (int q = first + tid; q < N; q += blockDim.x) accepted[order[q]] = 0; }
+    else { for (int k = tid; k < N; k += blockDim.x) accepted[k] = 0; }
+    if (tid == 0) nlive_s = first ? *nlive_io : 0;
     __syncthreads();
-    for (int base = 0; base < N; base += 1024) {     // ordered compaction, 1024 positions per pass
+    const int nlive0 = nlive_s;                      // live candidates the stored set already stands for
+    for (int base = first; base < N; base += 1024) {     // ordered compaction, 1024 positions per pass
         const int pos = base + tid;
         const int k = pos < N ? order[pos] : -1;
-        const bool keep = k >= 0 && ((bits[(size_t)k * words + (k >> 6)] >> (k & 63)) & 1ull);
+        const bool keep = k >= 0 && ((bits[(size_t)k * stride + (k >> 6)] >> (k & 63)) & 1ull);
         const unsigned long long m = __ballot(keep);
         if (lane == 0) wcount[wave] = __popcll(m);
         __syncthreads();
@@ -413,7 +522,7 @@ __global__ __launch_bounds__(1024) void k_set_max(int N, int words, const int* o
     }
     __threadfence_block();
     const int nlive = nlive_s;
-    for (int base = 0; base < nlive; base += RC) {
+    for (int base = nlive0; base < nlive; base += RC) {
         int k[CPW];
         bool bad[CPW];
 #pragma unroll
@@ -426,7 +535,7 @@ __global__ __launch_bounds__(1024) void k_set_max(int N, int words, const int* o
             const unsigned long long a = acc[w];
 #pragma unroll
             for (int c = 0; c < CPW; ++c) {
-                const unsigned long long r = k[c] >= 0 ? bits[(size_t)k[c] * words + w] : ~0ull;
+                const unsigned long long r = k[c] >= 0 ? bits[(size_t)k[c] * stride + w] : ~0ull;
                 bad[c] = bad[c] || (r & a) != a;
             }
         }
@@ -443,7 +552,7 @@ __global__ __launch_bounds__(1024) void k_set_max(int N, int words, const int* o
             unsigned m = 0;
             if (lane < RC && kk[lane] >= 0) {
                 const int o = kk[lane];
-                m = (unsigned)((bits[(size_t)k[c] * words + (o >> 6)] >> (o & 63)) & 1ull);
+                m = (unsigned)((bits[(size_t)k[c] * stride + (o >> 6)] >> (o & 63)) & 1ull);
             }
             const unsigned long long bal = __ballot(m != 0);
             if (lane == 0) conf[c * 16 + wave] = bal;
@@ -460,6 +569,10 @@ __global__ __launch_bounds__(1024) void k_set_max(int N, int words, const int* o
             }
         }
         __syncthreads();
+    }
+    if (mask) {
+        for (int w = tid; w < words; w += blockDim.x) mask[w] = acc[w];
+        if (tid == 0) *nlive_io = nlive;
     }
 }
 
@@ -637,6 +750,15 @@ struct ipc_engine {
     hipEvent_t ev_fork = nullptr, ev_join[kMaxSide] = {}, ev_join_own = nullptr;
     // scratch for ipc_run
     unsigned long long *d_upper = nullptr, *d_bits = nullptr; unsigned char* d_acc = nullptr; size_t run_cap = 0;
+    // Online matrix (ipc_run_online): the matrix over the first on_cov candidates stays on the device and an
+    // update solves the cells of the columns behind them.  Rows by the identity map, addressed by the capacity stride
+    // on_wcap = on_ccap / 64 words (on_ccap a multiple of 64 that doubles), so N crossing a multiple of 64 moves nothing.
+    int on_cov = 0, on_ccap = 0, on_wcap = 0, reserved_cands = 0;
+    unsigned long long *d_on_upper = nullptr, *d_on_bits = nullptr;     // [on_ccap][on_wcap] solved upper-triangle bits / symmetric matrix
+    unsigned long long* d_on_mask = nullptr;                            // [on_wcap] accepted mask the set-max resumes from
+    unsigned char* d_on_acc = nullptr;                                  // [on_ccap] accepted bytes
+    int* d_on_live = nullptr;                                           // [on_ccap + 1] compacted live list, [on_ccap] = its length
+    long online_growths = 0;
     // incremental mode / final map (SE2)
     std::vector<double> h_odom_meas, h_odom_info;      // file values, for the un-scaled chain
     std::vector<int> h_from, h_to, cns;
@@ -1043,6 +1165,7 @@ static void free_candidates(ipc_engine* h)
     h->retired.clear();
     h->d_cand = nullptr; h->d_from = h->d_to = h->d_lo = h->d_hi = h->d_order = h->d_live = nullptr;
     h->N = 0; h->cstride = 0; h->order_stale = false; h->cand_event = false;
+    h->on_cov = 0;                                       // (the online matrix's storage stays; its content is that of another list)
 }
 
 // candidate arrays for `cap` records (cap a multiple of 64); the record array zeroed on own_stream
@@ -1068,7 +1191,7 @@ static int alloc_candidates(ipc_engine* h, int cap)
 static int grow_candidates(ipc_engine* h, int need)
 {
     const int nf = h->dim == 2 ? (int)F_NFIELDS : (int)G_NFIELDS;
-    int cap = std::max(64, h->cstride);
+    int cap = std::max(std::max(64, h->cstride), h->reserved_cands);
     while (cap < need) cap *= 2;
     double* o_cand = h->d_cand; const int o_stride = h->cstride;
     int *o_from = h->d_from, *o_to = h->d_to, *o_lo = h->d_lo, *o_hi = h->d_hi, *o_order = h->d_order, *o_live = h->d_live, *o_perm = h->d_rowperm;
@@ -1080,6 +1203,15 @@ static int grow_candidates(ipc_engine* h, int need)
         HIPCHK(hipMemcpyAsync(h->d_to, o_to, sizeof(int) * h->N, hipMemcpyDeviceToDevice, h->own_stream));
         HIPCHK(hipMemcpyAsync(h->d_lo, o_lo, sizeof(int) * h->N, hipMemcpyDeviceToDevice, h->own_stream));
         HIPCHK(hipMemcpyAsync(h->d_hi, o_hi, sizeof(int) * h->N, hipMemcpyDeviceToDevice, h->own_stream));
+        // A list that is already in use moved (ipc_reserve_candidates after a run; an append repeats this for its own record):
+        // the other streams wait for the copies as they wait for an appended record, the row order of the planning pass lived in
+        // the old d_rowperm and is built again (ensure_row_map), and so is the plan that was made from it.  d_order and d_live
+        // are read by matrix-mode calls only, behind matrix_mode_enter, which re-sends the order (order_stale).
+        if (!h->ev_cand) HIPCHK(hipEventCreateWithFlags(&h->ev_cand, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(h->ev_cand, h->own_stream));
+        h->cand_event = true;
+        h->slot_world = 0;
+        h->plan_cached = false;
     }
     for (void* q : {(void*)o_cand, (void*)o_from, (void*)o_to, (void*)o_lo, (void*)o_hi, (void*)o_order, (void*)o_live, (void*)o_perm})
         if (q) h->retired.push_back(q);
@@ -1103,6 +1235,7 @@ extern "C" int ipc_destroy(ipc_engine_t* h)
     hipFree(h->d_chain); hipFree(h->d_chain_rec); hipFree(h->d_chain_blk); hipFree(h->d_pose0); hipFree(h->d_counters); hipFree(h->d_offsets); hipFree(h->d_wave_ctr);
     hipFree(h->d_cells); hipFree(h->d_chi); hipFree(h->d_chitot); hipFree(h->d_meta);
     hipFree(h->d_upper); hipFree(h->d_bits); hipFree(h->d_acc); hipFree(h->d_failed);
+    hipFree(h->d_on_upper); hipFree(h->d_on_bits); hipFree(h->d_on_mask); hipFree(h->d_on_acc); hipFree(h->d_on_live);
     hipFree(h->d_lit_cells); hipFree(h->d_lit_idx); hipFree(h->d_lit_chi); hipFree(h->d_lit_chitot); hipFree(h->d_lit_meta);
     hipFree(h->d_slot_off); hipFree(h->d_recount); if (h->h_recount) hipHostFree(h->h_recount);
     if (h->h_stage) hipHostFree(h->h_stage);
@@ -1209,7 +1342,7 @@ static int upload_candidates(ipc_engine* h, int n, const int* ids, const double*
     h->ppos.assign(n, 0);
     for (int q = 0; q < n; ++q) h->ppos[h->porder[q]] = q;
     if (n == 0) return IPC_OK;
-    if (int rc = alloc_candidates(h, (n + 63) & ~63)) return rc;
+    if (int rc = alloc_candidates(h, std::max((n + 63) & ~63, h->reserved_cands))) return rc;
     h->N = n;
     HIPCHK(hipMemcpy(h->d_from, h->h_from.data(), sizeof(int) * n, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->d_to, h->h_to.data(), sizeof(int) * n, hipMemcpyHostToDevice));
@@ -1650,6 +1783,72 @@ static int resolve_failed_cells(ipc_engine* h, int n)
 
 static int solve_rows_impl(ipc_engine* h, int rank, int world, uint64_t* d_upper, void* stream, int phase);
 
+// The cell lists of one solve: d_cells grouped by slot = (loop count, chain-length bin), counts / offsets per slot.
+constexpr int kPlanSlots = 2 * (kMaxBins + 1);
+struct CellPlan { unsigned counts[kPlanSlots], offsets[kPlanSlots]; size_t total = 0; };
+
+// Planning: count pass, ONE read-back, buffers, fill pass.  launch_pass(cells, fill) enqueues the planning kernel of the
+// caller (k_plan: the rows of a rank; k_plan_delta: the columns behind the online matrix) on `st`; both passes see the same
+// counter layout [slot][kPlanSub].  min_cap: the cell buffers hold at least that many cells (the online matrix asks for its
+// candidate capacity, so that an update within it allocates nothing).
+template <class LaunchPass>
+static int plan_cells(ipc_engine* h, hipStream_t st, CellPlan& pl, size_t min_cap, LaunchPass&& launch_pass)
+{
+    constexpr int NS = kPlanSlots;
+    unsigned* counts = pl.counts; unsigned* offsets = pl.offsets;
+    size_t total = 0;
+    h->plan_cached = false;
+    // pass 1: count
+    HIPCHK(hipMemsetAsync(h->d_counters, 0, sizeof(unsigned) * NS * kPlanSub, st));
+    launch_pass((int2*)nullptr, 0);
+    HIPCHK(hipGetLastError());
+    static thread_local unsigned subcounts[NS * kPlanSub], suboffsets[NS * kPlanSub];
+    HIPCHK(hipMemcpyAsync(subcounts, h->d_counters, sizeof subcounts, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int s = 0; s < NS; ++s) {
+        counts[s] = 0;
+        for (int q = 0; q < kPlanSub; ++q) counts[s] += subcounts[s * kPlanSub + q];
+    }
+    for (int s = 0; s < NS; ++s) { offsets[s] = (unsigned)total; total += counts[s]; }
+    for (int s = 0; s < NS; ++s) {                    // a slot's sub-lists are contiguous: one cell list per slot
+        unsigned o = offsets[s];
+        for (int q = 0; q < kPlanSub; ++q) { suboffsets[s * kPlanSub + q] = o; o += subcounts[s * kPlanSub + q]; }
+    }
+    if (std::max(total, min_cap) > h->cells_cap) {
+        hipFree(h->d_cells); hipFree(h->d_chi); hipFree(h->d_chitot); hipFree(h->d_meta);
+        hipFree(h->d_lit_cells); hipFree(h->d_lit_idx); hipFree(h->d_lit_chi); hipFree(h->d_lit_chitot); hipFree(h->d_lit_meta);
+        h->d_cells = h->d_lit_cells = nullptr; h->d_chi = h->d_chitot = h->d_lit_chi = h->d_lit_chitot = nullptr;
+        h->d_meta = h->d_lit_meta = nullptr; h->d_lit_idx = nullptr;
+        h->cells_cap = std::max(total + total / 8 + 1024, min_cap);
+        HIPCHK(hipMalloc(&h->d_cells, sizeof(int2) * h->cells_cap));
+        HIPCHK(hipMalloc(&h->d_chi, sizeof(double) * h->cells_cap));
+        HIPCHK(hipMalloc(&h->d_chitot, sizeof(double) * h->cells_cap));
+        HIPCHK(hipMalloc(&h->d_meta, sizeof(int4) * h->cells_cap));
+        HIPCHK(hipMalloc(&h->d_lit_cells, sizeof(int2) * h->cells_cap));
+        HIPCHK(hipMalloc(&h->d_lit_idx, sizeof(int) * (h->cells_cap + 1)));      // (+ 1: k_slow_flags / k_scan_int write and scan total + 1 entries)
+        HIPCHK(hipMalloc(&h->d_lit_chi, sizeof(double) * h->cells_cap));
+        HIPCHK(hipMalloc(&h->d_lit_chitot, sizeof(double) * h->cells_cap));
+        HIPCHK(hipMalloc(&h->d_lit_meta, sizeof(int4) * h->cells_cap));
+    }
+    if (!h->d_slot_off) {
+        HIPCHK(hipMalloc(&h->d_slot_off, sizeof(unsigned) * (NS + 1)));
+        HIPCHK(hipMalloc(&h->d_recount, sizeof(int) * (NS + 1)));
+        HIPCHK(hipHostMalloc(&h->h_recount, sizeof(int) * (NS + 1)));
+    }
+    // pass 2: fill
+    static thread_local unsigned slot_off[NS + 1];
+    for (int s = 0; s < NS; ++s) slot_off[s] = offsets[s];
+    slot_off[NS] = (unsigned)total;
+    HIPCHK(hipMemcpyAsync(h->d_slot_off, slot_off, sizeof slot_off, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(h->d_offsets, suboffsets, sizeof suboffsets, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(h->d_counters, 0, sizeof(unsigned) * NS * kPlanSub, st));
+    launch_pass(h->d_cells, 1);
+    HIPCHK(hipGetLastError());
+    pl.total = total;
+    return IPC_OK;
+}
+static int solve_planned(ipc_engine* h, hipStream_t st, const CellPlan& pl);
+
 extern "C" int ipc_solve_rows(ipc_engine_t* h, int rank, int world, uint64_t* d_upper, void* stream)
 {
     if (!h) return fail(IPC_ERR_ARG, "ipc_solve_rows: NULL handle");
@@ -1659,89 +1858,16 @@ extern "C" int ipc_solve_rows(ipc_engine_t* h, int rank, int world, uint64_t* d_
     return solve_rows_impl(h, rank, world, d_upper, stream, 0);
 }
 
-// phase 0: all cells of the rank's rows.  Set-only mode (one rank): phase 1 = the diagonal cells, phase 2 = the pair cells
-// among the candidates whose diagonal bit is set in d_upper (left in place; the pair bits are OR-ed into it).
-static int solve_rows_impl(ipc_engine* h, int rank, int world, uint64_t* d_upper, void* stream, int phase)
+// "Solve these planned lists": the bin launches over the engine's streams (fork / join around `st`), the cluster solver for
+// chains beyond every cell kernel, the collection of failed and borderline cells with its read-back, the literal re-solve and
+// the host-driven Levenberg retry.  One code path for the batch step (solve_rows_impl) and the online update
+// (ipc_run_online); the results are left in d_chi / d_chitot / d_meta beside d_cells.
+static int solve_planned(ipc_engine* h, hipStream_t st, const CellPlan& pl)
 {
-    HIPCHK(hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->own_stream;
-    const int N = h->N, words = (N + 63) / 64, rpr = ipc_rows_per_rank(N, world);
-    if (int rc = matrix_mode_enter(h, st)) return rc;
-    if (int rc = ensure_row_map(h, world)) return rc;
-    const BinCaps bc = h->plan.caps;
-    const int nb = bc.n;
-    constexpr int NS = 2 * (kMaxBins + 1);
-    if (phase != 2) HIPCHK(hipMemsetAsync(d_upper, 0, sizeof(uint64_t) * (size_t)rpr * words, st));
-    unsigned counts[NS], offsets[NS];
-    size_t total = 0;
-    // The cell lists of this rank (d_cells, grouped by slot = (loop count, chain-length bin)) depend on the candidates,
-    // the rank and the world only: a repeated step reuses them and skips the two planning passes with their read-back.
-    // (The set-only phases plan from the diagonal bits of the step and are never cached.)
-    const bool cached = phase == 0 && h->plan_cached && h->plan_rank == rank && h->plan_world == world;
-    if (cached) {
-        std::copy(h->plan_counts.begin(), h->plan_counts.end(), counts);
-        std::copy(h->plan_offsets.begin(), h->plan_offsets.end(), offsets);
-        total = h->plan_total;
-    } else {
-        h->plan_cached = false;
-        // pass 1: count
-        HIPCHK(hipMemsetAsync(h->d_counters, 0, sizeof(unsigned) * NS * kPlanSub, st));
-        const int nrows = h->row_group_off[rank + 1] - h->row_group_off[rank];
-        const int* rows = h->d_rowperm + h->row_group_off[rank];
-        const dim3 pgrid((N + 255) / 256, std::max(1, std::min(nrows, 2048))), pblock(256);     // few fat blocks: dispatching one block per (row, 256 candidates) cost more than the compares
-        hipLaunchKernelGGL(k_plan, pgrid, pblock, 0, st, N, h->d_lo, h->d_hi, rows, nrows, bc, h->d_counters,
-                           h->d_offsets, (int2*)nullptr, 0, phase, (const unsigned long long*)d_upper, words);
-        HIPCHK(hipGetLastError());
-        static thread_local unsigned subcounts[NS * kPlanSub], suboffsets[NS * kPlanSub];
-        HIPCHK(hipMemcpyAsync(subcounts, h->d_counters, sizeof subcounts, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (int s = 0; s < NS; ++s) {
-            counts[s] = 0;
-            for (int q = 0; q < kPlanSub; ++q) counts[s] += subcounts[s * kPlanSub + q];
-        }
-        for (int s = 0; s < NS; ++s) { offsets[s] = (unsigned)total; total += counts[s]; }
-        for (int s = 0; s < NS; ++s) {                    // a slot's sub-lists are contiguous: one cell list per slot
-            unsigned o = offsets[s];
-            for (int q = 0; q < kPlanSub; ++q) { suboffsets[s * kPlanSub + q] = o; o += subcounts[s * kPlanSub + q]; }
-        }
-        if (total > h->cells_cap) {
-            hipFree(h->d_cells); hipFree(h->d_chi); hipFree(h->d_chitot); hipFree(h->d_meta);
-            hipFree(h->d_lit_cells); hipFree(h->d_lit_idx); hipFree(h->d_lit_chi); hipFree(h->d_lit_chitot); hipFree(h->d_lit_meta);
-            h->d_cells = h->d_lit_cells = nullptr; h->d_chi = h->d_chitot = h->d_lit_chi = h->d_lit_chitot = nullptr;
-            h->d_meta = h->d_lit_meta = nullptr; h->d_lit_idx = nullptr;
-            h->cells_cap = total + total / 8 + 1024;
-            HIPCHK(hipMalloc(&h->d_cells, sizeof(int2) * h->cells_cap));
-            HIPCHK(hipMalloc(&h->d_chi, sizeof(double) * h->cells_cap));
-            HIPCHK(hipMalloc(&h->d_chitot, sizeof(double) * h->cells_cap));
-            HIPCHK(hipMalloc(&h->d_meta, sizeof(int4) * h->cells_cap));
-            HIPCHK(hipMalloc(&h->d_lit_cells, sizeof(int2) * h->cells_cap));
-            HIPCHK(hipMalloc(&h->d_lit_idx, sizeof(int) * (h->cells_cap + 1)));      // (+ 1: k_slow_flags / k_scan_int write and scan total + 1 entries)
-            HIPCHK(hipMalloc(&h->d_lit_chi, sizeof(double) * h->cells_cap));
-            HIPCHK(hipMalloc(&h->d_lit_chitot, sizeof(double) * h->cells_cap));
-            HIPCHK(hipMalloc(&h->d_lit_meta, sizeof(int4) * h->cells_cap));
-        }
-        if (!h->d_slot_off) {
-            HIPCHK(hipMalloc(&h->d_slot_off, sizeof(unsigned) * (NS + 1)));
-            HIPCHK(hipMalloc(&h->d_recount, sizeof(int) * (NS + 1)));
-            HIPCHK(hipHostMalloc(&h->h_recount, sizeof(int) * (NS + 1)));
-        }
-        // pass 2: fill
-        static thread_local unsigned slot_off[NS + 1];
-        for (int s = 0; s < NS; ++s) slot_off[s] = offsets[s];
-        slot_off[NS] = (unsigned)total;
-        HIPCHK(hipMemcpyAsync(h->d_slot_off, slot_off, sizeof slot_off, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(h->d_offsets, suboffsets, sizeof suboffsets, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemsetAsync(h->d_counters, 0, sizeof(unsigned) * NS * kPlanSub, st));
-        hipLaunchKernelGGL(k_plan, pgrid, pblock, 0, st, N, h->d_lo, h->d_hi, rows, nrows, bc, h->d_counters,
-                           h->d_offsets, h->d_cells, 1, phase, (const unsigned long long*)d_upper, words);
-        HIPCHK(hipGetLastError());
-        if (phase == 0) {
-            h->plan_counts.assign(counts, counts + NS);
-            h->plan_offsets.assign(offsets, offsets + NS);
-            h->plan_total = total; h->plan_rank = rank; h->plan_world = world;
-            h->plan_cached = true;
-        }
-    }
+    constexpr int NS = kPlanSlots;
+    const unsigned* counts = pl.counts; const unsigned* offsets = pl.offsets;
+    const size_t total = pl.total;
+    const int nb = h->plan.caps.n;
     // cells whose chain is longer than the largest kernel variant of the policy go through the cluster
     // solver below (one at a time, state in HBM: no length limit) instead of failing the matrix
     const unsigned n_long = counts[nb] + counts[(kMaxBins + 1) + nb];
@@ -1854,6 +1980,47 @@ static int solve_rows_impl(ipc_engine* h, int rank, int world, uint64_t* d_upper
             if (int rc = resolve_failed_cells(h, h->h_recount[NS])) return rc;
         }
     }
+    return IPC_OK;
+}
+
+// phase 0: all cells of the rank's rows.  Set-only mode (one rank): phase 1 = the diagonal cells, phase 2 = the pair cells
+// among the candidates whose diagonal bit is set in d_upper (left in place; the pair bits are OR-ed into it).
+static int solve_rows_impl(ipc_engine* h, int rank, int world, uint64_t* d_upper, void* stream, int phase)
+{
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->own_stream;
+    const int N = h->N, words = (N + 63) / 64, rpr = ipc_rows_per_rank(N, world);
+    if (int rc = matrix_mode_enter(h, st)) return rc;
+    if (int rc = ensure_row_map(h, world)) return rc;
+    const BinCaps bc = h->plan.caps;
+    constexpr int NS = kPlanSlots;
+    if (phase != 2) HIPCHK(hipMemsetAsync(d_upper, 0, sizeof(uint64_t) * (size_t)rpr * words, st));
+    CellPlan pl;
+    // The cell lists of this rank (d_cells, grouped by slot = (loop count, chain-length bin)) depend on the candidates,
+    // the rank and the world only: a repeated step reuses them and skips the two planning passes with their read-back.
+    // (The set-only phases plan from the diagonal bits of the step and are never cached.)
+    const bool cached = phase == 0 && h->plan_cached && h->plan_rank == rank && h->plan_world == world;
+    if (cached) {
+        std::copy(h->plan_counts.begin(), h->plan_counts.end(), pl.counts);
+        std::copy(h->plan_offsets.begin(), h->plan_offsets.end(), pl.offsets);
+        pl.total = h->plan_total;
+    } else {
+        const int nrows = h->row_group_off[rank + 1] - h->row_group_off[rank];
+        const int* rows = h->d_rowperm + h->row_group_off[rank];
+        const dim3 pgrid((N + 255) / 256, std::max(1, std::min(nrows, 2048))), pblock(256);     // few fat blocks: dispatching one block per (row, 256 candidates) cost more than the compares
+        if (int rc = plan_cells(h, st, pl, 0, [&](int2* cells, int fill) {
+                hipLaunchKernelGGL(k_plan, pgrid, pblock, 0, st, N, h->d_lo, h->d_hi, rows, nrows, bc, h->d_counters,
+                                   h->d_offsets, cells, fill, phase, (const unsigned long long*)d_upper, words);
+            })) return rc;
+        if (phase == 0) {
+            h->plan_counts.assign(pl.counts, pl.counts + NS);
+            h->plan_offsets.assign(pl.offsets, pl.offsets + NS);
+            h->plan_total = pl.total; h->plan_rank = rank; h->plan_world = world;
+            h->plan_cached = true;
+        }
+    }
+    const size_t total = pl.total;
+    if (int rc = solve_planned(h, st, pl)) return rc;
     if (total)
         hipLaunchKernelGGL(k_scatter_bits, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total,
                            h->d_cells, h->d_chi, h->prm.fast_reject_th, h->prm.slow_reject_th, rpr, (const int*)h->d_slot, words,
@@ -1901,8 +2068,8 @@ extern "C" int ipc_set_max(ipc_engine_t* h, const uint64_t* d_bits, uint8_t* d_a
     const size_t shmem = sizeof(unsigned long long) * words;
     if (shmem > 60 * 1024) return fail(IPC_ERR_LIMIT, "ipc_set_max: N=%d exceeds the LDS-resident mask", N);
     if (int rc = matrix_mode_enter(h, st)) return rc;
-    hipLaunchKernelGGL(k_set_max, dim3(1), dim3(1024), shmem, st, N, words, h->d_order,
-                       (const unsigned long long*)d_bits, d_accepted, h->d_live);
+    hipLaunchKernelGGL(k_set_max, dim3(1), dim3(1024), shmem, st, N, words, words, (const int*)h->d_order,
+                       (const unsigned long long*)d_bits, d_accepted, h->d_live, 0, (unsigned long long*)nullptr, (int*)nullptr);
     HIPCHK(hipGetLastError());
     return IPC_OK;
 }
@@ -1931,6 +2098,143 @@ extern "C" int ipc_run(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accepted_ou
     HIPCHK(hipStreamSynchronize(h->own_stream));
     if (bits_out) HIPCHK(hipMemcpy(bits_out, h->d_bits, sizeof(uint64_t) * need, hipMemcpyDeviceToHost));
     if (accepted_out) HIPCHK(hipMemcpy(accepted_out, h->d_acc, (size_t)N, hipMemcpyDeviceToHost));
+    return IPC_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// online matrix mode: the matrix stays on the device, an update solves the columns behind it
+// ------------------------------------------------------------------------------------------
+// Storage for `cap` candidates (a multiple of 64): the rows the matrix covers move to the wider stride on own_stream, the old
+// arrays are retired as grow_candidates retires the candidate arrays (freed with the next ipc_set_candidates or the engine).
+static int grow_online(ipc_engine* h, int cap)
+{
+    const int wcap = cap / 64, M = h->on_cov;
+    hipStream_t st = h->own_stream;
+    unsigned long long *n_upper = nullptr, *n_bits = nullptr, *n_mask = nullptr;
+    unsigned char* n_acc = nullptr; int* n_live = nullptr;
+    const size_t mat = sizeof(unsigned long long) * (size_t)cap * wcap;
+    size_t mem_free = 0, mem_total = 0;                  // (quadratic in the capacity: 2 x 512 MB at 65 536 candidates -- refused before anything is allocated)
+    HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
+    if (2 * mat + 16 * (size_t)cap > mem_free)
+        return fail(IPC_ERR_LIMIT, "online matrix for %d candidates needs %zu MB, the device has %zu MB free", cap, (2 * mat) >> 20, mem_free >> 20);
+    HIPCHK(hipMalloc(&n_upper, mat));
+    HIPCHK(hipMalloc(&n_bits, mat));
+    HIPCHK(hipMalloc(&n_mask, sizeof(unsigned long long) * wcap));
+    HIPCHK(hipMalloc(&n_acc, (size_t)cap));
+    HIPCHK(hipMalloc(&n_live, sizeof(int) * ((size_t)cap + 1)));
+    HIPCHK(hipMemsetAsync(n_upper, 0, mat, st));
+    HIPCHK(hipMemsetAsync(n_bits, 0, mat, st));
+    HIPCHK(hipMemsetAsync(n_mask, 0, sizeof(unsigned long long) * wcap, st));
+    HIPCHK(hipMemsetAsync(n_acc, 0, (size_t)cap, st));
+    HIPCHK(hipMemsetAsync(n_live, 0, sizeof(int) * ((size_t)cap + 1), st));
+    if (M > 0) {
+        const size_t opitch = sizeof(unsigned long long) * h->on_wcap, npitch = sizeof(unsigned long long) * wcap;
+        HIPCHK(hipMemcpy2DAsync(n_upper, npitch, h->d_on_upper, opitch, opitch, M, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpy2DAsync(n_bits, npitch, h->d_on_bits, opitch, opitch, M, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(n_mask, h->d_on_mask, opitch, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(n_acc, h->d_on_acc, (size_t)M, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(n_live, h->d_on_live, sizeof(int) * (size_t)M, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(n_live + cap, h->d_on_live + h->on_ccap, sizeof(int), hipMemcpyDeviceToDevice, st));
+    }
+    for (void* q : {(void*)h->d_on_upper, (void*)h->d_on_bits, (void*)h->d_on_mask, (void*)h->d_on_acc, (void*)h->d_on_live})
+        if (q) h->retired.push_back(q);
+    h->d_on_upper = n_upper; h->d_on_bits = n_bits; h->d_on_mask = n_mask; h->d_on_acc = n_acc; h->d_on_live = n_live;
+    h->on_ccap = cap; h->on_wcap = wcap;
+    ++h->online_growths;
+    return IPC_OK;
+}
+
+extern "C" int ipc_reserve_candidates(ipc_engine_t* h, int capacity)
+{
+    if (!h) return fail(IPC_ERR_ARG, "ipc_reserve_candidates: NULL handle");
+    if (capacity < 0 || capacity > (1 << 24)) return fail(IPC_ERR_ARG, "ipc_reserve_candidates: capacity %d (0 .. 2^24)", capacity);
+    HIPCHK(hipSetDevice(h->device));
+    const int cap = (capacity + 63) & ~63;
+    if (cap > h->reserved_cands) h->reserved_cands = cap;
+    if (cap > h->cstride) { if (int rc = grow_candidates(h, cap)) return rc; }
+    // (beyond the N limit of ipc_run_online only the candidate arrays are reserved: the faithful mode has no such limit)
+    if (cap > h->on_ccap && sizeof(unsigned long long) * (size_t)(cap / 64) <= 60 * 1024) { if (int rc = grow_online(h, cap)) return rc; }
+    return IPC_OK;
+}
+
+extern "C" int ipc_online_covered(ipc_engine_t* h, int* m)
+{
+    if (!h || !m) return fail(IPC_ERR_ARG, "ipc_online_covered: NULL argument");
+    *m = h->on_cov;
+    return IPC_OK;
+}
+
+extern "C" int ipc_online_reset(ipc_engine_t* h)
+{
+    if (!h) return fail(IPC_ERR_ARG, "ipc_online_reset: NULL handle");
+    h->on_cov = 0;                                       // (the next ipc_run_online clears the storage before it writes)
+    return IPC_OK;
+}
+
+extern "C" int ipc_run_online(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accepted_out, ipc_online_report_t* report)
+{
+    if (!h) return fail(IPC_ERR_ARG, "ipc_run_online: NULL handle");
+    if (h->N <= 0) return fail(IPC_ERR_STATE, "ipc_run_online: no candidates set");
+    HIPCHK(hipSetDevice(h->device));
+    const int N = h->N, M = h->on_cov, words = (N + 63) / 64;
+    if (sizeof(unsigned long long) * (size_t)words > 60 * 1024) return fail(IPC_ERR_LIMIT, "ipc_run_online: N=%d exceeds the LDS-resident mask", N);
+    hipStream_t st = h->own_stream;
+    if (int rc = matrix_mode_enter(h, st)) return rc;
+    ipc_online_report_t rep{};
+    rep.covered_before = M; rep.covered_after = N;
+    if (N > h->on_ccap) {
+        int cap = std::max(64, h->on_ccap);
+        while (cap < N) cap *= 2;
+        if (int rc = grow_online(h, cap)) return rc;
+        rep.grew = 1;
+    }
+    const int stride = h->on_wcap;
+    h->last_cells = 0; h->last_long_cells = 0; h->last_lm_cells = h->last_literal_cells = 0;
+    if (M < N) {
+        if (M == 0) {                                    // a whole solve: whatever an earlier list left in the storage goes
+            const size_t mat = sizeof(unsigned long long) * (size_t)h->on_ccap * stride;
+            HIPCHK(hipMemsetAsync(h->d_on_upper, 0, mat, st));
+            HIPCHK(hipMemsetAsync(h->d_on_bits, 0, mat, st));
+            HIPCHK(hipMemsetAsync(h->d_on_mask, 0, sizeof(unsigned long long) * stride, st));
+        }
+        // the cell lists and their results share d_cells & co. with the batch path: its cached plan is gone (plan_cells)
+        CellPlan pl;
+        const BinCaps bc = h->plan.caps;
+        const dim3 pgrid((N + 255) / 256, std::min(N - M, 2048)), pblock(256);
+        if (int rc = plan_cells(h, st, pl, (size_t)h->on_ccap, [&](int2* cells, int fill) {
+                hipLaunchKernelGGL(k_plan_delta, pgrid, pblock, 0, st, N, M, (const int*)h->d_lo, (const int*)h->d_hi, bc, h->d_counters,
+                                   (const unsigned*)h->d_offsets, cells, fill);
+            })) return rc;
+        const size_t total = pl.total;
+        if (int rc = solve_planned(h, st, pl)) return rc;
+        if (total)
+            hipLaunchKernelGGL(k_scatter_bits_delta, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total, (const int2*)h->d_cells,
+                               (const double*)h->d_chi, h->prm.fast_reject_th, h->prm.slow_reject_th, stride, h->d_on_upper);
+        const int tiles = ((N - 1) >> 6) + 1;
+        hipLaunchKernelGGL(k_assemble_delta, dim3(words, std::min((tiles + 3) / 4, 1024)), dim3(256), 0, st, N, M, stride, (const int*)h->d_lo,
+                           (const int*)h->d_hi, (const unsigned long long*)h->d_on_upper, h->d_on_bits);
+        // The greedy resumes when every newcomer sits behind every covered candidate in the processing order: the verdicts of
+        // the covered ones are then those of the whole run, and only the newcomers are tested -- against the stored set and
+        // against each other.  A newcomer that sorts in front of a covered candidate can change verdicts behind it: rerun.
+        bool resume = M > 0;
+        for (int q = M; q < N && resume; ++q) resume = h->order[q] >= M;
+        hipLaunchKernelGGL(k_set_max, dim3(1), dim3(1024), sizeof(unsigned long long) * words, st, N, words, stride, (const int*)h->d_order,
+                           (const unsigned long long*)h->d_on_bits, h->d_on_acc, h->d_on_live, resume ? M : 0, h->d_on_mask,
+                           h->d_on_live + h->on_ccap);
+        HIPCHK(hipGetLastError());
+        h->on_cov = N;
+        rep.cells = (int)total;
+        rep.long_cells = h->last_long_cells;
+        rep.literal_cells = h->last_literal_cells;
+        rep.damped_cells = h->last_lm_cells;
+        rep.set_max_resumed = resume ? 1 : 0;
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    if (bits_out)
+        HIPCHK(hipMemcpy2D(bits_out, sizeof(uint64_t) * words, h->d_on_bits, sizeof(uint64_t) * stride, sizeof(uint64_t) * words, N,
+                           hipMemcpyDeviceToHost));
+    if (accepted_out) HIPCHK(hipMemcpy(accepted_out, h->d_on_acc, (size_t)N, hipMemcpyDeviceToHost));
+    if (report) *report = rep;
     return IPC_OK;
 }
 
