@@ -380,6 +380,10 @@ int ipc_debug_absorbed_edges(int klo, int khi, int n, const int* lo, const int* 
  * bwb_out = half-bandwidth in blocks, order_out[nl] = the loops in band order, the border's wide loops last. */
 int ipc_debug_band_plan(int d, int nl, const int* a, const int* b, int min_n, int* use_out, int* nlb_out, int* bwb_out,
                         int* order_out);
+/* Device buffers, pinned host buffers and events the library's owning handles hold at this moment, in the whole process
+ * (out[0], out[1], out[2]; host code, no GPU): all zero once every engine is destroyed.  The per-device stream pool is not
+ * counted -- it lives as long as the process. */
+int ipc_debug_live_resources(int out[3]);
 
 #ifdef __cplusplus
 }

@@ -34,7 +34,7 @@ SYMBOLS = [
     "ipc_remove_from_consensus", "ipc_add_to_consensus", "ipc_current_poses", "ipc_final_optimize",
     "ipc_debug_dense_solve", "ipc_debug_band_solve", "ipc_debug_band_plan", "ipc_debug_absorbed_edges", "ipc_append_candidate", "ipc_incremental_set_state", "ipc_incremental_counters", "ipc_row_assignment", "ipc_run_sharded", "ipc_run_set_only",
     "ipc_append_odometry", "ipc_reserve_vertices", "ipc_vertex_count",
-    "ipc_run_online", "ipc_online_covered", "ipc_online_reset", "ipc_reserve_candidates",
+    "ipc_run_online", "ipc_online_covered", "ipc_online_reset", "ipc_reserve_candidates", "ipc_debug_live_resources",
 ]
 
 
@@ -141,6 +141,7 @@ def load():
     lib.ipc_debug_band_solve.argtypes = [ip, ip, ip, vp, ip, vp, C.POINTER(ip)]
     lib.ipc_debug_absorbed_edges.argtypes = [ip, ip, ip, vp, vp, ip, vp, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]
     lib.ipc_debug_band_plan.argtypes = [ip, ip, vp, vp, ip, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip), vp]
+    lib.ipc_debug_live_resources.argtypes = [C.POINTER(ip * 3)]
     assert C.sizeof(CellInfo) == CELL_DTYPE.itemsize
     _lib = lib
     return lib

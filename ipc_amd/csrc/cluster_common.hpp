@@ -12,6 +12,7 @@
 
 #include "block_prims.hpp"
 #include "dense_chol.hpp"
+#include "hip_owned.hpp"
 
 namespace ipc {
 

@@ -13,13 +13,12 @@ namespace ipc {
 struct LiteralBand {
     PoseBandPlan plan;
     BandLayout B{};
-    double* d_A = nullptr; size_t capA = 0;         // system + factor
-    double *d_dinv = nullptr, *d_x = nullptr; size_t capN = 0;
-    int* d_ublk = nullptr; size_t capU = 0;
-    PersistCtl* d_ctl = nullptr;
-    double* d_zero = nullptr;
+    DevBuf<double> d_A; size_t capA = 0;            // system + factor
+    DevBuf<double> d_dinv, d_x; size_t capN = 0;
+    DevBuf<int> d_ublk; size_t capU = 0;
+    DevBuf<PersistCtl> d_ctl;
+    DevBuf<double> d_zero;
     long solves = 0;
-    ~LiteralBand() { hipFree(d_A); hipFree(d_dinv); hipFree(d_x); hipFree(d_ublk); hipFree(d_ctl); hipFree(d_zero); }
 };
 inline void literal_band_free(LiteralBand* p) { delete p; }
 
@@ -64,10 +63,9 @@ hipError_t literal_band_damped(Solver& S, double lambda, bool& used, double* x_o
         W.plan = pose_band_plan(d, L, nl, lf, lf + nl);
         S.lband_stale = false;
         if (W.plan.use) {
-            if ((size_t)L + 1 > W.capU) {
-                hipFree(W.d_ublk); W.d_ublk = nullptr;
+            if (!W.d_ublk || (size_t)L + 1 > W.capU) {      // (a failed allocation leaves the handle empty: the next call comes here again)
                 W.capU = (size_t)L + 1 + L / 2;
-                IPC_CL_CHK(hipMalloc(&W.d_ublk, sizeof(int) * W.capU));
+                IPC_CL_CHK(W.d_ublk.alloc(W.capU));
             }
             IPC_CL_CHK(hipMemcpyAsync(W.d_ublk, W.plan.ublk.data(), sizeof(int) * ((size_t)L + 1), hipMemcpyHostToDevice, st));
             IPC_CL_CHK(hipStreamSynchronize(st));           // (the plan's vector may be rebuilt by the next solve)
@@ -79,21 +77,21 @@ hipError_t literal_band_damped(Solver& S, double lambda, bool& used, double* x_o
     if (!W.plan.use) return hipSuccess;
     const BandLayout B = W.B;
     if (B.doubles() >= ((size_t)1 << 31)) return hipSuccess;       // (32-bit addressing of the factorisation)
-    if (!W.d_ctl) {
-        IPC_CL_CHK(hipMalloc(&W.d_ctl, sizeof(PersistCtl)));
-        IPC_CL_CHK(hipMalloc(&W.d_zero, sizeof(double) * 8));
+    if (!W.d_zero) {
+        IPC_CL_CHK(W.d_ctl.alloc(1));
+        IPC_CL_CHK(W.d_zero.alloc(8));
         IPC_CL_CHK(hipMemsetAsync(W.d_zero, 0, sizeof(double) * 8, st));
     }
-    if (2 * B.doubles() > W.capA) {
-        hipFree(W.d_A); W.d_A = nullptr;
+    if (!W.d_A || 2 * B.doubles() > W.capA) {
         W.capA = 2 * B.doubles() + B.doubles() / 4;
-        IPC_CL_CHK(hipMalloc(&W.d_A, sizeof(double) * W.capA));
+        IPC_CL_CHK(W.d_A.alloc(W.capA));
     }
     if ((size_t)B.n + 64 > W.capN) {
-        hipFree(W.d_dinv); hipFree(W.d_x); W.d_dinv = W.d_x = nullptr;
-        W.capN = (size_t)B.n + 64 + B.n / 4;
-        IPC_CL_CHK(hipMalloc(&W.d_dinv, sizeof(double) * W.capN));
-        IPC_CL_CHK(hipMalloc(&W.d_x, sizeof(double) * W.capN));
+        const size_t want = (size_t)B.n + 64 + B.n / 4;
+        W.capN = 0;                                     // (until both are there: a failure part way comes here again)
+        IPC_CL_CHK(W.d_dinv.alloc(want));
+        IPC_CL_CHK(W.d_x.alloc(want));
+        W.capN = want;
     }
     IPC_CL_CHK(hipMemsetAsync(W.d_A, 0, sizeof(double) * 2 * B.doubles(), st));
     S.launch_literal_H(BandStore{W.d_A, B, W.d_ublk, d}, lambda);

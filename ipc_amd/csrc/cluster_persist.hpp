@@ -1093,7 +1093,7 @@ public:
         band_min_n = k.band_min_n; band_split_min = k.band_split_min; band_team_wgs = k.band_team_wgs;
         band_team_reject = k.band_team_reject; fault_every_ = k.fault_every;
     }
-    ~PersistSolver() { release(); }
+    ~PersistSolver() { if (st_) hipStreamSynchronize(st_); }   // (before the handles below free what a launch in flight uses)
     bool last_was_band() const { return last_band_; }
     const BandLayout& last_band_layout() const { return band_; }
 
@@ -1275,44 +1275,29 @@ private:
     int fault_every_ = 0; long fault_count_ = 0;
     BandLayout band_{}, band2_{};
     double device_us_ = 0.0;
-    double *d_edge_ = nullptr, *d_loop_ = nullptr, *d_S_ = nullptr, *d_dinv_ = nullptr;
-    double *d_gpart_ = nullptr, *d_gscan_ = nullptr;       // reduction partials / scan run totals of the band kernel
-    int* d_abort_seen_ = nullptr;
-    int* d_int_ = nullptr;
+    DevBuf<double> d_edge_, d_loop_, d_S_, d_dinv_;
+    DevBuf<double> d_gpart_, d_gscan_;          // reduction partials / scan run totals of the band kernel
+    DevBuf<int> d_abort_seen_, d_int_;
     static constexpr int kTabSlots = 8;
-    int* h_tab_[kTabSlots] = {};
-    hipEvent_t ev_tab_[kTabSlots] = {};
+    PinnedBuf<int> h_tab_[kTabSlots];
+    Event ev_tab_[kTabSlots];
     bool tab_used_[kTabSlots] = {};
     int tab_slot_ = 0;
-    PersistCtl* d_ctl_ = nullptr;
-    PersistOut *d_out_ = nullptr, *h_out_ = nullptr;
+    DevBuf<PersistCtl> d_ctl_;
+    DevBuf<PersistOut> d_out_;
+    PinnedBuf<PersistOut> h_out_;
     LoopTables tab_;
 
-    void release()
-    {
-        hipFree(d_edge_); hipFree(d_loop_); hipFree(d_S_); hipFree(d_dinv_); hipFree(d_int_); hipFree(d_ctl_); hipFree(d_out_);
-        hipFree(d_gpart_); hipFree(d_gscan_); hipFree(d_abort_seen_);
-        d_gpart_ = d_gscan_ = nullptr; d_abort_seen_ = nullptr; capS_ = 0;
-        if (st_) hipStreamSynchronize(st_);
-        if (h_out_) hipHostFree(h_out_);
-        for (int k = 0; k < kTabSlots; ++k) {
-            if (h_tab_[k]) hipHostFree(h_tab_[k]);
-            if (ev_tab_[k]) hipEventDestroy(ev_tab_[k]);
-            h_tab_[k] = nullptr; ev_tab_[k] = nullptr; tab_used_[k] = false;
-        }
-        d_edge_ = d_loop_ = d_S_ = d_dinv_ = nullptr; d_int_ = nullptr; d_ctl_ = nullptr; d_out_ = h_out_ = nullptr;
-        capL_ = capNl_ = 0;
-    }
     hipError_t ensure(int L, int nl, size_t sdoubles)
     {
-        if (!h_out_) {
-            IPC_CL_CHK(hipHostMalloc(&h_out_, sizeof(PersistOut)));
-            IPC_CL_CHK(hipMalloc(&d_out_, sizeof(PersistOut)));
-            IPC_CL_CHK(hipMalloc(&d_ctl_, sizeof(PersistCtl)));
-            IPC_CL_CHK(hipMalloc(&d_abort_seen_, sizeof(int) * 16));       // [0]: abort word as workgroup 0 saw it; [8..9]: a double 0.0
+        if (!ev_tab_[kTabSlots - 1]) {                             // (keyed on the LAST thing it creates: a failure part way runs it again)
+            IPC_CL_CHK(h_out_.alloc(1));
+            IPC_CL_CHK(d_out_.alloc(1));
+            IPC_CL_CHK(d_ctl_.alloc(1));
+            IPC_CL_CHK(d_abort_seen_.alloc(16));                   // [0]: abort word as workgroup 0 saw it; [8..9]: a double 0.0
             IPC_CL_CHK(hipMemset(d_abort_seen_, 0, sizeof(int) * 16));
             IPC_CL_CHK(hipStreamSynchronize(nullptr));             // (NULL-stream memsets are not ordered against the non-blocking streams the solves run on)
-            for (int k = 0; k < kTabSlots; ++k) IPC_CL_CHK(hipEventCreateWithFlags(&ev_tab_[k], hipEventDisableTiming));
+            for (int k = 0; k < kTabSlots; ++k) IPC_CL_CHK(ev_tab_[k].create(hipEventDisableTiming));
         }
         if (L > capL_ || nl > capNl_) {
             // (hipFree waits for the whole device, i.e. for every other solve in flight: grow in big steps -- the clusters
@@ -1320,25 +1305,22 @@ private:
             const int nL = L > capL_ ? std::max(L, capL_ + capL_ / 2) : capL_;
             const int nN = nl > capNl_ ? std::max(std::max(nl, 48), capNl_ + capNl_ / 2) : capNl_;
             if (st_) IPC_CL_CHK(hipStreamSynchronize(st_));        // (a launch in flight still uses the old workspaces)
-            hipFree(d_edge_); hipFree(d_loop_); hipFree(d_dinv_); hipFree(d_int_); hipFree(d_gpart_); hipFree(d_gscan_);
-            for (int k = 0; k < kTabSlots; ++k) { if (h_tab_[k]) hipHostFree(h_tab_[k]); h_tab_[k] = nullptr; tab_used_[k] = false; }
-            d_edge_ = d_loop_ = d_dinv_ = d_gpart_ = d_gscan_ = nullptr; d_int_ = nullptr;
             capL_ = capNl_ = 0;
             const size_t ld = (size_t)nL + 2, n = (size_t)T::kD * nN;
-            IPC_CL_CHK(hipMalloc(&d_edge_, sizeof(double) * (T::kEdgeDoubles * ld + ld + nN)));
-            IPC_CL_CHK(hipMalloc(&d_loop_, sizeof(double) * (T::kLoopDoubles * (size_t)nN + 8)));
-            IPC_CL_CHK(hipMalloc(&d_dinv_, sizeof(double) * (2 * n + 4 * kCB)));      // (a split factorisation keeps two systems' pivots)
-            IPC_CL_CHK(hipMalloc(&d_int_, sizeof(int) * LoopTables::capacity(nL, nN)));
-            IPC_CL_CHK(hipMalloc(&d_gpart_, sizeof(double) * 2 * 8 * ((ld + nN + 255) / 256 + 2)));
-            IPC_CL_CHK(hipMalloc(&d_gscan_, sizeof(double) * 27 * ((ld + 1023) / 1024 + 2)));
-            for (int k = 0; k < kTabSlots; ++k) IPC_CL_CHK(hipHostMalloc(&h_tab_[k], sizeof(int) * LoopTables::capacity(nL, nN)));
+            IPC_CL_CHK(d_edge_.alloc(T::kEdgeDoubles * ld + ld + nN));
+            IPC_CL_CHK(d_loop_.alloc(T::kLoopDoubles * (size_t)nN + 8));
+            IPC_CL_CHK(d_dinv_.alloc(2 * n + 4 * kCB));            // (a split factorisation keeps two systems' pivots)
+            IPC_CL_CHK(d_int_.alloc(LoopTables::capacity(nL, nN)));
+            IPC_CL_CHK(d_gpart_.alloc(2 * 8 * ((ld + nN + 255) / 256 + 2)));
+            IPC_CL_CHK(d_gscan_.alloc(27 * ((ld + 1023) / 1024 + 2)));
+            for (int k = 0; k < kTabSlots; ++k) { tab_used_[k] = false; IPC_CL_CHK(h_tab_[k].alloc(LoopTables::capacity(nL, nN))); }
             capL_ = nL; capNl_ = nN;
         }
         if (sdoubles > capS_) {
             const size_t want = std::max(sdoubles + sdoubles / 4, 2 * capS_);      // (hipFree waits for the whole device: few, large steps)
             if (st_) IPC_CL_CHK(hipStreamSynchronize(st_));
-            hipFree(d_S_); d_S_ = nullptr; capS_ = 0;
-            IPC_CL_CHK(hipMalloc(&d_S_, sizeof(double) * want));
+            capS_ = 0;
+            IPC_CL_CHK(d_S_.alloc(want));
             capS_ = want;
         }
         return hipSuccess;

@@ -739,7 +739,7 @@ __global__ void gk3_quad_bh(ClusterDev3 D)
 // ------------------------------------------------------------------------------------------
 class ClusterSolver3 {
 public:
-    ~ClusterSolver3() { release(); }
+    ~ClusterSolver3() { if (lband) literal_band_free(lband); }
     double term_eps = 0.0;             // convergence shortcut of the trial loop (Se2View::term_eps)
 
     // src: poses [12][src_ld] with global indexing; the optimised poses stay in result() ([12][ld()],
@@ -776,26 +776,18 @@ public:
     }
 
 private:
-    double* d_H_ = nullptr; size_t capH_ = 0;
+    DevBuf<double> d_H_; size_t capH_ = 0;
     ClusterDev3 dev_{};
     hipStream_t st_ = nullptr;
     int nblk_ = 1;
     std::vector<double>* chi_host_ = nullptr;
     int capL_ = 0, capNl_ = 0;
-    double *d_edge_ = nullptr, *d_loop_ = nullptr, *d_S_ = nullptr, *d_partial_ = nullptr, *d_scal_ = nullptr;
-    int *d_int_ = nullptr, *d_info_ = nullptr;
-    double* h_scal_ = nullptr;
+    DevBuf<double> d_edge_, d_loop_, d_S_, d_partial_, d_scal_;
+    DevBuf<int> d_int_;
+    int* d_info_ = nullptr;             // inside d_scal_
+    PinnedBuf<double> h_scal_;
     LoopTables tab_;
 
-    void release()
-    {
-        if (lband) { literal_band_free(lband); lband = nullptr; }
-        hipFree(d_edge_); hipFree(d_loop_); hipFree(d_S_); hipFree(d_partial_); hipFree(d_scal_);
-        hipFree(d_int_); hipFree(d_H_); d_H_ = nullptr; capH_ = 0;
-        if (h_scal_) hipHostFree(h_scal_);
-        d_edge_ = d_loop_ = d_S_ = d_partial_ = d_scal_ = nullptr; d_int_ = d_info_ = nullptr; h_scal_ = nullptr;
-        capL_ = capNl_ = 0;
-    }
     hipError_t ensure(int L, int nl);
     hipError_t fetch(int n)
     {
@@ -819,22 +811,20 @@ private:
 
 inline hipError_t ClusterSolver3::ensure(int L, int nl)
 {
-    if (!h_scal_) {
-        IPC_CL_CHK(hipHostMalloc(&h_scal_, sizeof(double) * 16));
-        IPC_CL_CHK(hipMalloc(&d_scal_, sizeof(double) * 16));
+    if (!d_scal_) {                                  // (the last thing the block creates: a failure part way runs it again)
+        IPC_CL_CHK(h_scal_.alloc(16));
+        IPC_CL_CHK(d_scal_.alloc(16));
         d_info_ = reinterpret_cast<int*>(d_scal_ + 12);
     }
     if (L > capL_ || nl > capNl_) {
         const int nL = std::max(L, capL_), nN = std::max(nl, capNl_);
-        hipFree(d_edge_); hipFree(d_loop_); hipFree(d_S_); hipFree(d_partial_); hipFree(d_int_);
-        d_edge_ = d_loop_ = d_S_ = d_partial_ = nullptr; d_int_ = nullptr;
         capL_ = capNl_ = 0;
         const size_t ld = (size_t)nL + 2;
-        IPC_CL_CHK(hipMalloc(&d_edge_, sizeof(double) * (99 * ld + ld + nN)));
-        IPC_CL_CHK(hipMalloc(&d_loop_, sizeof(double) * (72 * (size_t)nN + 8)));
-        IPC_CL_CHK(hipMalloc(&d_S_, sizeof(double) * 2 * (6 * (size_t)nN + 1) * (6 * (size_t)nN)));   // system + factor
-        IPC_CL_CHK(hipMalloc(&d_partial_, sizeof(double) * 4 * ((nL + nN + 1 + kGB) / kGB + 1)));
-        IPC_CL_CHK(hipMalloc(&d_int_, sizeof(int) * LoopTables::capacity(nL, nN)));
+        IPC_CL_CHK(d_edge_.alloc(99 * ld + ld + nN));
+        IPC_CL_CHK(d_loop_.alloc(72 * (size_t)nN + 8));
+        IPC_CL_CHK(d_S_.alloc(2 * (6 * (size_t)nN + 1) * (6 * (size_t)nN)));   // system + factor
+        IPC_CL_CHK(d_partial_.alloc(4 * ((nL + nN + 1 + kGB) / kGB + 1)));
+        IPC_CL_CHK(d_int_.alloc(LoopTables::capacity(nL, nN)));
         capL_ = nL; capNl_ = nN;
     }
     return hipSuccess;
@@ -888,8 +878,8 @@ inline hipError_t ClusterSolver3::damped_solve(double lambda, bool& ok, double& 
         if (n > kMaxDenseN) return hipSuccess;                   // (no band and too large for the dense store: the solve reports Fail)
         const size_t m = (size_t)(n + 1) * n;
         if (2 * m > capH_) {
-            hipFree(d_H_); d_H_ = nullptr; capH_ = 0;
-            IPC_CL_CHK(hipMalloc(&d_H_, sizeof(double) * 2 * m));
+            capH_ = 0;
+            IPC_CL_CHK(d_H_.alloc(2 * m));
             capH_ = 2 * m;
         }
         IPC_CL_CHK(hipMemsetAsync(d_H_, 0, sizeof(double) * m, st_));

@@ -16,6 +16,7 @@
 #include <cstring>
 #include <numeric>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <chrono>
@@ -695,40 +696,46 @@ static hipError_t launch_se3_lds(int nl, int idx, int n, hipStream_t st, const S
 }
 
 struct ipc_engine {
+    // The engine's one stream of its own.  FIRST member, so that it dies LAST: the solvers below wait for their last launch
+    // on it when they die, and every buffer and event goes before the stream does.
+    struct OwnStream {
+        hipStream_t s = nullptr;
+        ~OwnStream() { if (s) hipStreamDestroy(s); }
+        operator hipStream_t() const { return s; }
+    } own_stream;
     int dim = 2, V = 0, N = 0, device = 0;
     // V is the vertex COUNT of the moment; the pose arrays ([3 | 5 | 12][vcap]) are addressed by their capacity vcap >= V and
     // the chain arrays by estride >= V - 1, so that ipc_append_odometry grows the chain in place (DESIGN.md "Online chain")
     int vcap = 0;
-    double* h_stage = nullptr; double* d_stage = nullptr; size_t stage_cap = 0;   // pinned staging of an append of several edges
-    hipEvent_t ev_stage = nullptr; bool stage_used = false;                       // behind the kernel that read it last
+    PinnedBuf<double> h_stage; double* d_stage = nullptr; size_t stage_cap = 0;   // pinned staging of an append of several edges (d_stage: its device address)
+    Event ev_stage; bool stage_used = false;                                     // behind the kernel that read it last
     long chain_growths = 0;
     ipc_params_t prm{};
     double term_eps = 1e-13;                           // IPC_TERMINATE_EPS (0: g2o's literal trial loop), Se2View::term_eps
     BinPlan plan{};
-    hipStream_t own_stream = nullptr;
     // chain
-    double* d_chain = nullptr; int estride = 0;
-    double* d_chain_rec = nullptr;                     // record-major copy [estride + 64][F_NFIELDS | G_NFIELDS]
-    double2* d_chain_blk = nullptr;                    // SE3: blocked copy [estride / 64 + 2][kSe3BlkPairs][64]
-    double* d_pose0 = nullptr;
+    DevBuf<double> d_chain; int estride = 0;
+    DevBuf<double> d_chain_rec;                        // record-major copy [estride + 64][F_NFIELDS | G_NFIELDS]
+    DevBuf<double2> d_chain_blk;                       // SE3: blocked copy [estride / 64 + 2][kSe3BlkPairs][64]
+    DevBuf<double> d_pose0;
     // candidates
-    double* d_cand = nullptr; int cstride = 0;        // cstride = capacity in records (>= N): the list grows in place
-    int *d_from = nullptr, *d_to = nullptr, *d_lo = nullptr, *d_hi = nullptr, *d_order = nullptr;
-    int* d_live = nullptr;                             // set-max: candidates with a set diagonal bit, in processing order
-    int* d_rowperm = nullptr;                          // rows grouped by owning rank (of slot_world), each group in the order the planning pass visits them (by first vertex, then index)
+    DevBuf<double> d_cand; int cstride = 0;           // cstride = capacity in records (>= N): the list grows in place
+    DevBuf<int> d_from, d_to, d_lo, d_hi, d_order;
+    DevBuf<int> d_live;                                // set-max: candidates with a set diagonal bit, in processing order
+    DevBuf<int> d_rowperm;                             // rows grouped by owning rank (of slot_world), each group in the order the planning pass visits them (by first vertex, then index)
     std::vector<int> row_group_off;                    // [world + 1] offsets of the groups
     bool order_stale = false;                          // d_order is behind `order` (appends): re-sent by the next matrix-mode call
-    std::vector<void*> retired;                        // candidate arrays a growth replaced while solves in flight may still read them
-    hipEvent_t ev_cand = nullptr; bool cand_event = false;   // behind the last record written by ipc_append_candidate (own_stream)
+    std::vector<DevBuf<void>> retired;                 // candidate arrays a growth replaced while solves in flight may still read them
+    Event ev_cand; bool cand_event = false;                 // behind the last record written by ipc_append_candidate (own_stream)
     std::vector<int> order, h_lo, h_hi;
     std::vector<int> h_cand_ids; std::vector<double> h_cand_meas, h_cand_info;   // raw candidate records in file order
     // plan / results of the last solve
-    unsigned* d_counters = nullptr;   // [2*(kMaxBins+1)]
-    unsigned* d_offsets = nullptr;
-    unsigned* d_wave_ctr = nullptr;   // work-queue heads of the wave-kernel launches, one per (nl, bin)
+    DevBuf<unsigned> d_counters;      // [2*(kMaxBins+1)]
+    DevBuf<unsigned> d_offsets;
+    DevBuf<unsigned> d_wave_ctr;      // work-queue heads of the wave-kernel launches, one per (nl, bin)
     int n_cu = 256;
-    int2* d_cells = nullptr; size_t cells_cap = 0;
-    double *d_chi = nullptr, *d_chitot = nullptr; int4* d_meta = nullptr;
+    DevBuf<int2> d_cells; size_t cells_cap = 0;
+    DevBuf<double> d_chi, d_chitot; DevBuf<int4> d_meta;
     // The cell lists of (rank, world) change only with the candidates: the two planning passes and their read-back (the
     // first of ipc_solve_rows' two host waits) are paid once per candidate list, not once per step (round 5).
     bool plan_cached = false; int plan_rank = -1, plan_world = 0; size_t plan_total = 0;
@@ -736,42 +743,43 @@ struct ipc_engine {
     std::vector<unsigned> plan_counts, plan_offsets;
     // Borderline cells (borderline_band) are solved again with g2o's literal trial loop BY THE CELL KERNELS (term_eps 0)
     // over compact per-slot lists built on the device -- no per-cell copies, no host-driven solves (round 5).
-    int2* d_lit_cells = nullptr; int* d_lit_idx = nullptr; double *d_lit_chi = nullptr, *d_lit_chitot = nullptr; int4* d_lit_meta = nullptr;
-    unsigned* d_slot_off = nullptr;                    // [slots + 1] first cell of each (loop count, bin) slot
-    int* d_recount = nullptr; int* h_recount = nullptr;   // [slots] borderline cells per slot, then the failed-cell count; pinned copy
+    DevBuf<int2> d_lit_cells; DevBuf<int> d_lit_idx; DevBuf<double> d_lit_chi, d_lit_chitot; DevBuf<int4> d_lit_meta;
+    DevBuf<unsigned> d_slot_off;                       // [slots + 1] first cell of each (loop count, bin) slot
+    DevBuf<int> d_recount; PinnedBuf<int> h_recount;      // [slots] borderline cells per slot, then the failed-cell count; pinned copy
     int last_cells = 0, last_long_cells = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr; bool ev_valid = false; int last_launches = 0;
+    Event ev0, ev1; bool ev_valid = false; int last_launches = 0;
     // side streams: the bin launches of one solve are spread over them so that the tail of one
     // launch (a few cells that run to the iteration cap) overlaps the next bins
     static constexpr int kMaxSide = 7;
     int n_side = 0;
     bool side_forced = false;                          // IPC_SIDE_STREAMS given: used as is, whatever the size of the step
     hipStream_t side[kMaxSide] = {};
-    hipEvent_t ev_fork = nullptr, ev_join[kMaxSide] = {}, ev_join_own = nullptr;
+    Event ev_fork, ev_join[kMaxSide], ev_join_own;
     // scratch for ipc_run
-    unsigned long long *d_upper = nullptr, *d_bits = nullptr; unsigned char* d_acc = nullptr; size_t run_cap = 0;
+    DevBuf<uint64_t> d_upper, d_bits; DevBuf<unsigned char> d_acc; size_t run_cap = 0;
     // Online matrix (ipc_run_online): the matrix over the first on_cov candidates stays on the device and an
     // update solves the cells of the columns behind them.  Rows by the identity map, addressed by the capacity stride
     // on_wcap = on_ccap / 64 words (on_ccap a multiple of 64 that doubles), so N crossing a multiple of 64 moves nothing.
     int on_cov = 0, on_ccap = 0, on_wcap = 0, reserved_cands = 0;
-    unsigned long long *d_on_upper = nullptr, *d_on_bits = nullptr;     // [on_ccap][on_wcap] solved upper-triangle bits / symmetric matrix
-    unsigned long long* d_on_mask = nullptr;                            // [on_wcap] accepted mask the set-max resumes from
-    unsigned char* d_on_acc = nullptr;                                  // [on_ccap] accepted bytes
-    int* d_on_live = nullptr;                                           // [on_ccap + 1] compacted live list, [on_ccap] = its length
+    DevBuf<unsigned long long> d_on_upper, d_on_bits;                   // [on_ccap][on_wcap] solved upper-triangle bits / symmetric matrix
+    DevBuf<unsigned long long> d_on_mask;                               // [on_wcap] accepted mask the set-max resumes from
+    DevBuf<unsigned char> d_on_acc;                                     // [on_ccap] accepted bytes
+    DevBuf<int> d_on_live;                                              // [on_ccap + 1] compacted live list, [on_ccap] = its length
     long online_growths = 0;
     // incremental mode / final map (SE2)
     std::vector<double> h_odom_meas, h_odom_info;      // file values, for the un-scaled chain
     std::vector<int> h_from, h_to, cns;
-    double* d_chain1 = nullptr;                        // chain records with (info * s) / s
-    double* d_open = nullptr;                          // [5][vcap] open-loop x y th cos sin
-    double* d_cur = nullptr;                           // [5][vcap] current estimates + kPoseTrail doubles (the tail transform, k_apply_accept)
-    ClusterSolver2* cluster = nullptr;
-    ClusterSolver3* cluster3 = nullptr;                // SE3: d_open is d_pose0 itself, d_cur is [12][V]
+    DevBuf<double> d_chain1;                           // chain records with (info * s) / s
+    double* d_open = nullptr;                          // [5][vcap] open-loop x y th cos sin: d_open_own, or d_pose0 itself (SE3)
+    DevBuf<double> d_open_own;
+    DevBuf<double> d_cur;                              // [5][vcap] current estimates + kPoseTrail doubles (the tail transform, k_apply_accept)
+    std::unique_ptr<ClusterSolver2> cluster;
+    std::unique_ptr<ClusterSolver3> cluster3;                // SE3: d_open is d_pose0 itself, d_cur is [12][V]
     // device-resident dog-leg (cluster_persist.hpp): the default; IPC_CLUSTER_MODE=host keeps the host-driven kernels
     bool persist = true;
     bool last_persist = false;                         // which solver holds the poses of the last cluster solve
-    int* d_slot = nullptr; int slot_world = 0; int row_policy = 1;    // row -> shard slot of the last world size (IPC_ROW_BALANCE=cyclic|cost)
-    int* d_failed = nullptr; int failed_cap = 0; int last_lm_cells = 0;    // cells of the last solve redone with Levenberg damping
+    DevBuf<int> d_slot; int slot_world = 0; int row_policy = 1;    // row -> shard slot of the last world size (IPC_ROW_BALANCE=cyclic|cost)
+    DevBuf<int> d_failed; int failed_cap = 0; int last_lm_cells = 0;    // cells of the last solve redone with Levenberg damping
     bool lm_retry = true;                              // IPC_LM_RETRY=0: a failed linear solve ends the optimisation (flags & 2), no damping
     // Cells whose max chi2 ends within this relative distance of their threshold are solved again with g2o's literal
     // trial loop (term_eps 0): the convergence test can move an edge's chi2 by up to 2 sqrt(term_eps) relative,
@@ -782,9 +790,9 @@ struct ipc_engine {
     long persist_timeouts = 0;                         // persistent launches whose grid barrier gave up (lost launches)
     long persist_relaunches = 0;                       // ... that were launched again (cluster_solve: twice before the host-driven solver)
     bool cns_dups = false;                             // some edge sits in the consensus set more than once (an accepted re-check, src/consensus.cpp:70)
-    PersistSolver<PersistSe2>* persist2 = nullptr;
-    PersistSolver<PersistSe3>* persist3 = nullptr;
-    unsigned long long* d_prof = nullptr;              // IPC_PERSIST_PROF=1: phase clocks of the persistent kernel's leader, printed by ipc_destroy
+    std::unique_ptr<PersistSolver<PersistSe2>> persist2;
+    std::unique_ptr<PersistSolver<PersistSe3>> persist3;
+    DevBuf<unsigned long long> d_prof;                 // IPC_PERSIST_PROF=1: phase clocks of the persistent kernel's leader, printed by ipc_destroy
     int max_helpers = -1;                              // IPC_PERSIST_HELPERS
     PersistKnobs knobs;                                            // IPC_BAND_* / IPC_PERSIST_FAULT_EVERY as they stood at ipc_create: every solver instance of the engine gets them
     int literal_band_min_n = 3072;                     // IPC_LITERAL_BAND_MIN_N, likewise
@@ -798,10 +806,10 @@ struct ipc_engine {
     // one-at-a-time loop takes.  An accept nobody assumed tells the later solves to stop (host-mapped word) and they are
     // redone from the new state.
     struct SpecSlot {
-        PersistSolver<PersistSe2>* s2 = nullptr;
-        PersistSolver<PersistSe3>* s3 = nullptr;
-        hipStream_t st = nullptr;
-        hipEvent_t done = nullptr;                     // behind the result copy of the solve in flight
+        std::unique_ptr<PersistSolver<PersistSe2>> s2;
+        std::unique_ptr<PersistSolver<PersistSe3>> s3;
+        hipStream_t st = nullptr;                      // (the process's: pipeline_stream)
+        Event done;                                    // behind the result copy of the solve in flight
         int cand = -1, pos = -1;                       // candidate / processing position of the solve in flight, -1: idle
         int state = -1;                                // index of the pose state it started from (spec_states)
         int launch_id = 0;
@@ -813,17 +821,18 @@ struct ipc_engine {
         double pred_ratio = -1.0;                      // the candidate's own chi2 at the state it starts from / the slow threshold (IPC_SPEC_LOG)
     };
     struct SpecState {                                 // a pose state solves start from
-        double* d_poses = nullptr;                     // d_cur (not owned) or a buffer of its own, [5 | 12][vcap] + kPoseTrail
+        double* d_poses = nullptr;                     // d_cur (not owned) or own_poses, [5 | 12][vcap] + kPoseTrail
+        DevBuf<double> own_poses;
         bool owned = false;
-        hipEvent_t ready = nullptr;                    // its poses are complete (recorded on the stream that wrote them)
+        Event ready;                                   // its poses are complete (recorded on the stream that wrote them)
         bool has_ready = false;
         std::vector<int> cns;                          // the consensus set it stands for
         int pos = -1;                                  // the accept at this processing position on top of its parent
         int users = 0;                                 // solves in flight that read it
         bool live = false;                             // committed, or in the tentative chain
         // predictions: every candidate's own chi2 at these poses (k_cand_own_chi2), copied to pinned host memory
-        double* d_pred = nullptr; double* h_pred = nullptr; int pred_cap = 0, pred_n = 0;
-        hipEvent_t pred_ev = nullptr; bool has_pred = false, pred_ready = false;
+        double* d_pred = nullptr; PinnedBuf<double> h_pred; int pred_cap = 0, pred_n = 0;   // (d_pred: the device address of h_pred)
+        Event pred_ev; bool has_pred = false, pred_ready = false;
     };
     struct SpecResult {                                // a finished solve waiting for its candidate's turn
         bool valid = false, agree = false, retry_host = false;
@@ -874,8 +883,8 @@ struct ipc_engine {
     double st_acc_s = 0, st_rej_s = 0; long st_acc_it = 0, st_rej_it = 0, st_acc_n = 0, st_rej_n = 0;   // IPC_SPEC_STATS
     double st_acc_dev_s = 0, st_rej_dev_s = 0;         // the same solves by the leader's own clock
     unsigned long long commit_count = 0;
-    hipEvent_t ev_commit = nullptr;
-    int* h_abort = nullptr;                            // host-mapped: one word per slot, the launch id to give up
+    Event ev_commit;
+    PinnedBuf<int> h_abort;                            // host-mapped: one word per slot, the launch id to give up
     int* d_abort = nullptr;
     int next_launch_id = 1;
     long spec_hits = 0, spec_launches = 0, spec_wasted = 0, spec_tentative = 0, spec_promoted = 0;
@@ -887,6 +896,10 @@ struct ipc_engine {
     FILE* spec_log = nullptr;                          // IPC_SPEC_LOG=<file>: one line per finished solve / tentative state / verdict handed out (tools/spec_chain.py)
     std::chrono::steady_clock::time_point spec_log_t0;
     long pred_conf[3][2] = {{0, 0}, {0, 0}, {0, 0}};   // [expectation + 1][verdict] over the solves whose result was kept (IPC_SPEC_STATS)
+
+    // Every buffer, pinned buffer, event and solver above releases itself (hip_owned.hpp), own_stream after all of them; what needs an
+    // order or has side effects is ipc_destroy's.  side[], pred_stream and the slots' streams belong to the process.
+    ~ipc_engine() { if (spec_log) fclose(spec_log); }
 };
 
 static int spec_quiesce(ipc_engine* h, bool state_changes);
@@ -1022,25 +1035,24 @@ extern "C" int ipc_create(int dim, int n_vertices, const double* odom_meas, cons
     HIPCHK(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(IPC_ERR_ARG, "ipc_create: device %d of %d", device, ndev);
     HIPCHK(hipSetDevice(device));
-    ipc_engine* h = new ipc_engine();
+    std::unique_ptr<ipc_engine> h(new ipc_engine());           // (every early return below releases what the engine holds by then)
     h->dim = dim; h->V = h->vcap = n_vertices; h->prm = *params; h->device = device;
     {
         std::string perr;
-        if (!make_plan(h->plan, dim, perr)) { delete h; return fail(IPC_ERR_ARG, "%s", perr.c_str()); }
+        if (!make_plan(h->plan, dim, perr)) return fail(IPC_ERR_ARG, "%s", perr.c_str());
     }
     if (const char* te = getenv("IPC_TERMINATE_EPS")) {
         if (*te) {
             char* end = nullptr;
             h->term_eps = strtod(te, &end);                          // "1e-13x", "off": refused, not read as 0
             while (end && (*end == ' ' || *end == '\t')) ++end;
-            if (end == te || (end && *end)) { delete h; return fail(IPC_ERR_ARG, "IPC_TERMINATE_EPS: '%s' is not a number", te); }
+            if (end == te || (end && *end)) return fail(IPC_ERR_ARG, "IPC_TERMINATE_EPS: '%s' is not a number", te);
         }
-        if (!(h->term_eps >= 0) || h->term_eps > 1e-6) { delete h; return fail(IPC_ERR_ARG, "IPC_TERMINATE_EPS must be in [0, 1e-6]"); }
+        if (!(h->term_eps >= 0) || h->term_eps > 1e-6) return fail(IPC_ERR_ARG, "IPC_TERMINATE_EPS must be in [0, 1e-6]");
     }
     if (const char* pp = getenv("IPC_PERSIST_PROF")) {
         if (*pp && strcmp(pp, "0")) {
-            if (hipMalloc(&h->d_prof, sizeof(unsigned long long) * kProfN) != hipSuccess) h->d_prof = nullptr;
-            else hipMemset(h->d_prof, 0, sizeof(unsigned long long) * kProfN);
+            if (h->d_prof.alloc(kProfN) == hipSuccess) hipMemset(h->d_prof, 0, sizeof(unsigned long long) * kProfN);
             hipStreamSynchronize(nullptr);                             // (NULL-stream copies are not ordered against the engine's non-blocking streams: copy_d2d_now)
         }
     }
@@ -1052,16 +1064,14 @@ extern "C" int ipc_create(int dim, int n_vertices, const double* odom_meas, cons
         if (*bb) {
             char* end = nullptr;
             h->borderline_band = strtod(bb, &end);
-            if (end == bb || *end || !(h->borderline_band >= 0) || h->borderline_band > 0.5) {
-                delete h;
+            if (end == bb || *end || !(h->borderline_band >= 0) || h->borderline_band > 0.5)
                 return fail(IPC_ERR_ARG, "IPC_BORDERLINE_BAND must be a number in [0, 0.5]");
-            }
         }
     }
     if (const char* sf = getenv("IPC_SLOW_FIRST")) { if (*sf) h->slow_first_iterations = std::max(0, atoi(sf)); }
     if (const char* rb = getenv("IPC_ROW_BALANCE")) {
         if (!strcmp(rb, "cyclic")) h->row_policy = 0;
-        else if (*rb && strcmp(rb, "cost")) { delete h; return fail(IPC_ERR_ARG, "IPC_ROW_BALANCE must be 'cost' or 'cyclic'"); }
+        else if (*rb && strcmp(rb, "cost")) return fail(IPC_ERR_ARG, "IPC_ROW_BALANCE must be 'cost' or 'cyclic'");
     }
     {   // window: as many solves in flight as there are hardware queues to run them side by side (IPC_SPEC_WINDOW overrides)
         const char* q = getenv("GPU_MAX_HW_QUEUES");
@@ -1080,44 +1090,44 @@ extern "C" int ipc_create(int dim, int n_vertices, const double* odom_meas, cons
     if (const char* gr = getenv("IPC_SPEC_GATE_MS")) { if (*gr) h->gate_release_ms = std::max(0.0, atof(gr)); }
     if (const char* cm = getenv("IPC_CLUSTER_MODE")) {
         if (!strcmp(cm, "host")) h->persist = false;
-        else if (*cm && strcmp(cm, "persist")) { delete h; return fail(IPC_ERR_ARG, "IPC_CLUSTER_MODE must be 'persist' or 'host'"); }
+        else if (*cm && strcmp(cm, "persist")) return fail(IPC_ERR_ARG, "IPC_CLUSTER_MODE must be 'persist' or 'host'");
     }
     const int E = n_vertices - 1;
     const int ms = dim == 2 ? 3 : 7, is = dim == 2 ? 6 : 21, nf = dim == 2 ? (int)F_NFIELDS : (int)G_NFIELDS;
     const int ps = dim == 2 ? 3 : 12;
     h->estride = (E + 63) & ~63;
-    HIPCHK(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreate(&h->ev0));
-    HIPCHK(hipEventCreate(&h->ev1));
+    HIPCHK(hipStreamCreateWithFlags(&h->own_stream.s, hipStreamNonBlocking));
+    HIPCHK(h->ev0.create());
+    HIPCHK(h->ev1.create());
     {
         const char* env = getenv("IPC_SIDE_STREAMS");
         h->n_side = env && *env ? atoi(env) : (h->dim == 2 ? kDefaultSideStreams2 : kDefaultSideStreams3);
         h->side_forced = env && *env;
         if (h->n_side < 0) h->n_side = 0;
         if (h->n_side > ipc_engine::kMaxSide) h->n_side = ipc_engine::kMaxSide;
-        HIPCHK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&h->ev_join_own, hipEventDisableTiming));
+        HIPCHK(h->ev_fork.create(hipEventDisableTiming));
+        HIPCHK(h->ev_join_own.create(hipEventDisableTiming));
         // the side streams come from the per-device pool of the PROCESS, the one the pipeline's slots use (the pipeline is
         // quiesced before any matrix-mode launch, matrix_mode_enter): an engine owns one stream, so how many engines are
         // alive no longer decides whether the runtime's couple of dozen usable streams are exceeded (round 5)
         for (int k = 0; k < h->n_side; ++k) {
             HIPCHK(pipeline_stream(device, k, &h->side[k]));
-            HIPCHK(hipEventCreateWithFlags(&h->ev_join[k], hipEventDisableTiming));
+            HIPCHK(h->ev_join[k].create(hipEventDisableTiming));
         }
     }
-    HIPCHK(hipMalloc(&h->d_chain, sizeof(double) * (nf * (size_t)h->estride + 64)));   // + read-ahead padding
-    HIPCHK(hipMalloc(&h->d_pose0, sizeof(double) * ps * (size_t)n_vertices));
-    HIPCHK(hipMalloc(&h->d_counters, sizeof(unsigned) * 2 * (kMaxBins + 1) * kPlanSub));
-    HIPCHK(hipMalloc(&h->d_offsets, sizeof(unsigned) * 2 * (kMaxBins + 1) * kPlanSub));
-    HIPCHK(hipMalloc(&h->d_wave_ctr, sizeof(unsigned) * 2 * (kMaxBins + 1)));
+    HIPCHK(h->d_chain.alloc(nf * (size_t)h->estride + 64));   // + read-ahead padding
+    HIPCHK(h->d_pose0.alloc(ps * (size_t)n_vertices));
+    HIPCHK(h->d_counters.alloc(2 * (kMaxBins + 1) * kPlanSub));
+    HIPCHK(h->d_offsets.alloc(2 * (kMaxBins + 1) * kPlanSub));
+    HIPCHK(h->d_wave_ctr.alloc(2 * (kMaxBins + 1)));
     {
         hipDeviceProp_t prop;
         HIPCHK(hipGetDeviceProperties(&prop, device));
         h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
-    double *d_m = nullptr, *d_i = nullptr;
-    HIPCHK(hipMalloc(&d_m, sizeof(double) * ms * E));
-    HIPCHK(hipMalloc(&d_i, sizeof(double) * is * E));
+    DevBuf<double> d_m, d_i;
+    HIPCHK(d_m.alloc((size_t)ms * E));
+    HIPCHK(d_i.alloc((size_t)is * E));
     HIPCHK(hipMemcpy(d_m, odom_meas, sizeof(double) * ms * E, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_i, odom_info, sizeof(double) * is * E, hipMemcpyHostToDevice));
     HIPCHK(hipStreamSynchronize(nullptr));                     // (NULL-stream copies are not ordered against the engine's non-blocking streams: copy_d2d_now)
@@ -1127,7 +1137,7 @@ extern "C" int ipc_create(int dim, int n_vertices, const double* odom_meas, cons
                            params->s_factor, h->d_chain, h->estride);
         hipLaunchKernelGGL(k_se2_propagate, dim3(1), dim3(64), 0, h->own_stream, n_vertices, h->d_chain, h->estride,
                            h->d_pose0, h->vcap);
-        HIPCHK(hipMalloc(&h->d_chain_rec, sizeof(double) * (size_t)F_NFIELDS * (h->estride + 64)));
+        HIPCHK(h->d_chain_rec.alloc((size_t)F_NFIELDS * (h->estride + 64)));
         HIPCHK(hipMemsetAsync(h->d_chain_rec, 0, sizeof(double) * (size_t)F_NFIELDS * (h->estride + 64), h->own_stream));
         hipLaunchKernelGGL(k_records, dim3((E + 255) / 256), dim3(256), 0, h->own_stream, E, (int)F_NFIELDS, h->d_chain,
                            h->estride, h->d_chain_rec);
@@ -1136,34 +1146,35 @@ extern "C" int ipc_create(int dim, int n_vertices, const double* odom_meas, cons
                            params->s_factor, h->d_chain, h->estride);
         hipLaunchKernelGGL(k_se3_propagate, dim3(1), dim3(64), 0, h->own_stream, n_vertices, h->d_chain, h->estride,
                            h->d_pose0, h->vcap);
-        HIPCHK(hipMalloc(&h->d_chain_rec, sizeof(double) * (size_t)G_NFIELDS * (h->estride + 64)));
+        HIPCHK(h->d_chain_rec.alloc((size_t)G_NFIELDS * (h->estride + 64)));
         HIPCHK(hipMemsetAsync(h->d_chain_rec, 0, sizeof(double) * (size_t)G_NFIELDS * (h->estride + 64), h->own_stream));
         hipLaunchKernelGGL(k_records, dim3((E + 255) / 256), dim3(256), 0, h->own_stream, E, (int)G_NFIELDS, h->d_chain,
                            h->estride, h->d_chain_rec);
         const size_t nblk = (size_t)h->estride / 64 + 2;
-        HIPCHK(hipMalloc(&h->d_chain_blk, sizeof(double2) * nblk * kSe3BlkPairs * 64));
+        HIPCHK(h->d_chain_blk.alloc(nblk * kSe3BlkPairs * 64));
         HIPCHK(hipMemsetAsync(h->d_chain_blk, 0, sizeof(double2) * nblk * kSe3BlkPairs * 64, h->own_stream));
         hipLaunchKernelGGL(k_se3_blocks, dim3((E + 255) / 256), dim3(256), 0, h->own_stream, E, h->d_chain, h->estride,
                            h->d_chain_blk);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->own_stream));
-    HIPCHK(hipFree(d_m));
-    HIPCHK(hipFree(d_i));
     h->h_odom_meas.assign(odom_meas, odom_meas + (size_t)ms * E);
     h->h_odom_info.assign(odom_info, odom_info + (size_t)is * E);
-    *out = h;
+    *out = h.release();
     return IPC_OK;
 }
 
+// An array that solves in flight may still read leaves its handle for the retired list (hipFree would wait for every one of
+// them): it dies with the next full upload (free_candidates) or with the engine.
+template <class T>
+static void retire(ipc_engine* h, DevBuf<T>& b) { if (b) h->retired.emplace_back(b.release()); }
+
 static void free_candidates(ipc_engine* h)
 {
-    hipFree(h->d_cand); hipFree(h->d_from); hipFree(h->d_to); hipFree(h->d_lo); hipFree(h->d_hi); hipFree(h->d_order); hipFree(h->d_live);
-    hipFree(h->d_rowperm); h->d_rowperm = nullptr;
-    hipFree(h->d_slot); h->d_slot = nullptr; h->slot_world = 0;
-    for (void* q : h->retired) hipFree(q);
+    h->d_cand.reset();
+    for (DevBuf<int>* b : {&h->d_from, &h->d_to, &h->d_lo, &h->d_hi, &h->d_order, &h->d_live, &h->d_rowperm, &h->d_slot}) b->reset();
+    h->slot_world = 0;
     h->retired.clear();
-    h->d_cand = nullptr; h->d_from = h->d_to = h->d_lo = h->d_hi = h->d_order = h->d_live = nullptr;
     h->N = 0; h->cstride = 0; h->order_stale = false; h->cand_event = false;
     h->on_cov = 0;                                       // (the online matrix's storage stays; its content is that of another list)
 }
@@ -1172,14 +1183,8 @@ static void free_candidates(ipc_engine* h)
 static int alloc_candidates(ipc_engine* h, int cap)
 {
     const int nf = h->dim == 2 ? (int)F_NFIELDS : (int)G_NFIELDS;
-    HIPCHK(hipMalloc(&h->d_cand, sizeof(double) * nf * (size_t)cap));
-    HIPCHK(hipMalloc(&h->d_from, sizeof(int) * cap));
-    HIPCHK(hipMalloc(&h->d_to, sizeof(int) * cap));
-    HIPCHK(hipMalloc(&h->d_lo, sizeof(int) * cap));
-    HIPCHK(hipMalloc(&h->d_hi, sizeof(int) * cap));
-    HIPCHK(hipMalloc(&h->d_order, sizeof(int) * cap));
-    HIPCHK(hipMalloc(&h->d_live, sizeof(int) * cap));
-    HIPCHK(hipMalloc(&h->d_rowperm, sizeof(int) * cap));
+    HIPCHK(h->d_cand.alloc(nf * (size_t)cap));
+    for (DevBuf<int>* b : {&h->d_from, &h->d_to, &h->d_lo, &h->d_hi, &h->d_order, &h->d_live, &h->d_rowperm}) HIPCHK(b->alloc(cap));
     HIPCHK(hipMemsetAsync(h->d_cand, 0, sizeof(double) * nf * (size_t)cap, h->own_stream));
     h->cstride = cap;
     return IPC_OK;
@@ -1193,8 +1198,11 @@ static int grow_candidates(ipc_engine* h, int need)
     const int nf = h->dim == 2 ? (int)F_NFIELDS : (int)G_NFIELDS;
     int cap = std::max(std::max(64, h->cstride), h->reserved_cands);
     while (cap < need) cap *= 2;
-    double* o_cand = h->d_cand; const int o_stride = h->cstride;
-    int *o_from = h->d_from, *o_to = h->d_to, *o_lo = h->d_lo, *o_hi = h->d_hi, *o_order = h->d_order, *o_live = h->d_live, *o_perm = h->d_rowperm;
+    // (retired before anything can fail: no return below frees an array that a solve in flight may read)
+    const double* o_cand = h->d_cand; const int o_stride = h->cstride;
+    const int *o_from = h->d_from, *o_to = h->d_to, *o_lo = h->d_lo, *o_hi = h->d_hi;
+    retire(h, h->d_cand);
+    for (DevBuf<int>* b : {&h->d_from, &h->d_to, &h->d_lo, &h->d_hi, &h->d_order, &h->d_live, &h->d_rowperm}) retire(h, *b);
     if (int rc = alloc_candidates(h, cap)) return rc;
     if (h->N > 0) {
         HIPCHK(hipMemcpy2DAsync(h->d_cand, sizeof(double) * cap, o_cand, sizeof(double) * o_stride, sizeof(double) * h->N, nf,
@@ -1207,14 +1215,12 @@ static int grow_candidates(ipc_engine* h, int need)
         // the other streams wait for the copies as they wait for an appended record, the row order of the planning pass lived in
         // the old d_rowperm and is built again (ensure_row_map), and so is the plan that was made from it.  d_order and d_live
         // are read by matrix-mode calls only, behind matrix_mode_enter, which re-sends the order (order_stale).
-        if (!h->ev_cand) HIPCHK(hipEventCreateWithFlags(&h->ev_cand, hipEventDisableTiming));
+        if (!h->ev_cand) HIPCHK(h->ev_cand.create(hipEventDisableTiming));
         HIPCHK(hipEventRecord(h->ev_cand, h->own_stream));
         h->cand_event = true;
         h->slot_world = 0;
         h->plan_cached = false;
     }
-    for (void* q : {(void*)o_cand, (void*)o_from, (void*)o_to, (void*)o_lo, (void*)o_hi, (void*)o_order, (void*)o_live, (void*)o_perm})
-        if (q) h->retired.push_back(q);
     h->order_stale = true;
     return IPC_OK;
 }
@@ -1231,18 +1237,6 @@ extern "C" int ipc_destroy(ipc_engine_t* h)
         if (dp.active == h) dp.active = nullptr;
         dp.engines.erase(std::remove(dp.engines.begin(), dp.engines.end(), h), dp.engines.end());
     }
-    free_candidates(h);
-    hipFree(h->d_chain); hipFree(h->d_chain_rec); hipFree(h->d_chain_blk); hipFree(h->d_pose0); hipFree(h->d_counters); hipFree(h->d_offsets); hipFree(h->d_wave_ctr);
-    hipFree(h->d_cells); hipFree(h->d_chi); hipFree(h->d_chitot); hipFree(h->d_meta);
-    hipFree(h->d_upper); hipFree(h->d_bits); hipFree(h->d_acc); hipFree(h->d_failed);
-    hipFree(h->d_on_upper); hipFree(h->d_on_bits); hipFree(h->d_on_mask); hipFree(h->d_on_acc); hipFree(h->d_on_live);
-    hipFree(h->d_lit_cells); hipFree(h->d_lit_idx); hipFree(h->d_lit_chi); hipFree(h->d_lit_chitot); hipFree(h->d_lit_meta);
-    hipFree(h->d_slot_off); hipFree(h->d_recount); if (h->h_recount) hipHostFree(h->h_recount);
-    if (h->h_stage) hipHostFree(h->h_stage);
-    if (h->ev_stage) hipEventDestroy(h->ev_stage);
-    hipFree(h->d_chain1); if (h->d_open != h->d_pose0) hipFree(h->d_open); hipFree(h->d_cur);
-    delete h->cluster;
-    delete h->cluster3;
     if (h->d_prof) {
         unsigned long long p[kProfN] = {};
         hipDeviceSynchronize();
@@ -1255,20 +1249,9 @@ extern "C" int ipc_destroy(ipc_engine_t* h)
         for (int k = 0; k < kProfN; ++k)
             fprintf(stderr, "%s\"%s\": %.1f", k ? ", " : "", names[k], (k == kProfIterations || k == kProfSteps || k == kProfStartLaunches) ? (double)p[k] : p[k] * 0.01);
         fprintf(stderr, "}}\n");
-        hipFree(h->d_prof);
     }
-    for (auto& sl : h->slots) {
-        if (sl.st) hipStreamSynchronize(sl.st);
-        delete sl.s2; delete sl.s3;
-        if (sl.done) hipEventDestroy(sl.done);
-        // (sl.st belongs to the process: pipeline_stream)
-    }
-    for (auto& stt : h->spec_states) {
-        if (stt.owned) hipFree(stt.d_poses);
-        if (stt.ready) hipEventDestroy(stt.ready);
-        if (stt.h_pred) hipHostFree(stt.h_pred);
-        if (stt.pred_ev) hipEventDestroy(stt.pred_ev);
-    }
+    for (auto& sl : h->slots)
+        if (sl.st) hipStreamSynchronize(sl.st);            // (before the slots' solvers die with the engine)
     if (h->d_prof || getenv("IPC_SPEC_STATS"))
         fprintf(stderr, "{\"speculation\": {\"window\": %d, \"slots_in_use\": %d, \"streams_abreast\": %d, \"persist_timeouts\": %ld, \"ahead\": %d, \"launches\": %ld, \"results_used\": %ld, \"discarded\": %ld, "
                         "\"tentative_states\": %ld, \"promoted\": %ld, \"host_s_in_checks\": %.3f, \"host_s_launching\": %.3f, "
@@ -1286,20 +1269,6 @@ extern "C" int ipc_destroy(ipc_engine_t* h)
                 (double)h->idle_why[0] / std::max(1ull, h->idle_why[4]), (double)h->idle_why[1] / std::max(1ull, h->idle_why[4]),
                 (double)h->idle_why[2] / std::max(1ull, h->idle_why[4]), (double)h->idle_why[3] / std::max(1ull, h->idle_why[4]),
                 h->pred_conf[2][1], h->pred_conf[2][0], h->pred_conf[1][1], h->pred_conf[1][0], h->pred_conf[0][1], h->pred_conf[0][0]);
-    if (h->spec_log) fclose(h->spec_log);
-    if (h->ev_commit) hipEventDestroy(h->ev_commit);
-    if (h->h_abort) hipHostFree(h->h_abort);
-    delete h->persist2;
-    delete h->persist3;
-    if (h->ev0) hipEventDestroy(h->ev0);
-    if (h->ev1) hipEventDestroy(h->ev1);
-    if (h->ev_fork) hipEventDestroy(h->ev_fork);
-    if (h->ev_join_own) hipEventDestroy(h->ev_join_own);
-    for (int k = 0; k < h->n_side; ++k) {
-        if (h->ev_join[k]) hipEventDestroy(h->ev_join[k]);
-        // (side[k] belongs to the process's stream pool)
-    }
-    if (h->own_stream) hipStreamDestroy(h->own_stream);
     delete h;
     return IPC_OK;
 }
@@ -1349,9 +1318,9 @@ static int upload_candidates(ipc_engine* h, int n, const int* ids, const double*
     HIPCHK(hipMemcpy(h->d_lo, h->h_lo.data(), sizeof(int) * n, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->d_hi, h->h_hi.data(), sizeof(int) * n, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->d_order, h->order.data(), sizeof(int) * n, hipMemcpyHostToDevice));
-    double *d_m = nullptr, *d_i = nullptr;
-    HIPCHK(hipMalloc(&d_m, sizeof(double) * ms * n));
-    HIPCHK(hipMalloc(&d_i, sizeof(double) * is * n));
+    DevBuf<double> d_m, d_i;
+    HIPCHK(d_m.alloc((size_t)ms * n));
+    HIPCHK(d_i.alloc((size_t)is * n));
     HIPCHK(hipMemcpy(d_m, meas, sizeof(double) * ms * n, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_i, info, sizeof(double) * is * n, hipMemcpyHostToDevice));
     HIPCHK(hipStreamSynchronize(nullptr));                     // (NULL-stream copies are not ordered against the engine's non-blocking streams: copy_d2d_now)
@@ -1363,8 +1332,6 @@ static int upload_candidates(ipc_engine* h, int n, const int* ids, const double*
                            h->d_cand, h->cstride);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->own_stream));
-    HIPCHK(hipFree(d_m));
-    HIPCHK(hipFree(d_i));
     return IPC_OK;
 }
 
@@ -1394,7 +1361,7 @@ extern "C" int ipc_append_candidate(ipc_engine_t* h, const int* ids, const doubl
         return fail(IPC_ERR_ARG, "candidate %d joins adjacent vertices %d-%d (an odometry edge, reference src/utils.cpp:184)", k, f, t);
     HIPCHK(hipSetDevice(h->device));
     if (k + 1 > h->cstride) { if (int rc = grow_candidates(h, k + 1)) return rc; }
-    if (!h->ev_cand) HIPCHK(hipEventCreateWithFlags(&h->ev_cand, hipEventDisableTiming));
+    if (!h->ev_cand) HIPCHK(h->ev_cand.create(hipEventDisableTiming));
     RawCandidate r{};
     for (int q = 0; q < ms; ++q) r.meas[q] = meas[q];
     for (int q = 0; q < is; ++q) r.info[q] = info[q];
@@ -1420,7 +1387,7 @@ extern "C" int ipc_append_candidate(ipc_engine_t* h, const int* ids, const doubl
     h->last_cells = 0;                                   // the cells of the last matrix solve are those of the shorter list
     h->plan_cached = false;
     h->ev_valid = false;
-    if (h->d_slot) { h->retired.push_back(h->d_slot); h->d_slot = nullptr; }
+    retire(h, h->d_slot);
     h->slot_world = 0;
     {
         std::lock_guard<std::recursive_mutex> run_lk(device_pipeline(h->device).run_mu);
@@ -1612,7 +1579,7 @@ static int ensure_row_map(ipc_engine* h, int world)
     if (h->d_slot && h->slot_world == world) return IPC_OK;
     std::vector<int> slot(h->N);
     if (int rc = ipc_row_assignment(h->N, h->h_cand_ids.data(), world, h->row_policy, slot.data())) return rc;
-    if (!h->d_slot) HIPCHK(hipMalloc(&h->d_slot, sizeof(int) * h->N));
+    if (!h->d_slot) HIPCHK(h->d_slot.alloc(h->N));
     HIPCHK(hipMemcpy(h->d_slot, slot.data(), sizeof(int) * h->N, hipMemcpyHostToDevice));
     // the rows of each rank, in the order its planning pass visits them: by the first vertex of the candidate's interval,
     // then by index (cell lists sorted by chain position, see k_plan)
@@ -1815,25 +1782,23 @@ static int plan_cells(ipc_engine* h, hipStream_t st, CellPlan& pl, size_t min_ca
         for (int q = 0; q < kPlanSub; ++q) { suboffsets[s * kPlanSub + q] = o; o += subcounts[s * kPlanSub + q]; }
     }
     if (std::max(total, min_cap) > h->cells_cap) {
-        hipFree(h->d_cells); hipFree(h->d_chi); hipFree(h->d_chitot); hipFree(h->d_meta);
-        hipFree(h->d_lit_cells); hipFree(h->d_lit_idx); hipFree(h->d_lit_chi); hipFree(h->d_lit_chitot); hipFree(h->d_lit_meta);
-        h->d_cells = h->d_lit_cells = nullptr; h->d_chi = h->d_chitot = h->d_lit_chi = h->d_lit_chitot = nullptr;
-        h->d_meta = h->d_lit_meta = nullptr; h->d_lit_idx = nullptr;
-        h->cells_cap = std::max(total + total / 8 + 1024, min_cap);
-        HIPCHK(hipMalloc(&h->d_cells, sizeof(int2) * h->cells_cap));
-        HIPCHK(hipMalloc(&h->d_chi, sizeof(double) * h->cells_cap));
-        HIPCHK(hipMalloc(&h->d_chitot, sizeof(double) * h->cells_cap));
-        HIPCHK(hipMalloc(&h->d_meta, sizeof(int4) * h->cells_cap));
-        HIPCHK(hipMalloc(&h->d_lit_cells, sizeof(int2) * h->cells_cap));
-        HIPCHK(hipMalloc(&h->d_lit_idx, sizeof(int) * (h->cells_cap + 1)));      // (+ 1: k_slow_flags / k_scan_int write and scan total + 1 entries)
-        HIPCHK(hipMalloc(&h->d_lit_chi, sizeof(double) * h->cells_cap));
-        HIPCHK(hipMalloc(&h->d_lit_chitot, sizeof(double) * h->cells_cap));
-        HIPCHK(hipMalloc(&h->d_lit_meta, sizeof(int4) * h->cells_cap));
+        const size_t cap = std::max(total + total / 8 + 1024, min_cap);
+        h->cells_cap = 0;                                // (until all nine are there: a failure part way comes here again)
+        HIPCHK(h->d_cells.alloc(cap));
+        HIPCHK(h->d_chi.alloc(cap));
+        HIPCHK(h->d_chitot.alloc(cap));
+        HIPCHK(h->d_meta.alloc(cap));
+        HIPCHK(h->d_lit_cells.alloc(cap));
+        HIPCHK(h->d_lit_idx.alloc(cap + 1));             // (+ 1: k_slow_flags / k_scan_int write and scan total + 1 entries)
+        HIPCHK(h->d_lit_chi.alloc(cap));
+        HIPCHK(h->d_lit_chitot.alloc(cap));
+        HIPCHK(h->d_lit_meta.alloc(cap));
+        h->cells_cap = cap;
     }
-    if (!h->d_slot_off) {
-        HIPCHK(hipMalloc(&h->d_slot_off, sizeof(unsigned) * (NS + 1)));
-        HIPCHK(hipMalloc(&h->d_recount, sizeof(int) * (NS + 1)));
-        HIPCHK(hipHostMalloc(&h->h_recount, sizeof(int) * (NS + 1)));
+    if (!h->h_recount) {                                 // (the last of the three)
+        HIPCHK(h->d_slot_off.alloc(NS + 1));
+        HIPCHK(h->d_recount.alloc(NS + 1));
+        HIPCHK(h->h_recount.alloc(NS + 1));
     }
     // pass 2: fill
     static thread_local unsigned slot_off[NS + 1];
@@ -1940,11 +1905,9 @@ static int solve_planned(ipc_engine* h, hipStream_t st, const CellPlan& pl)
         // The cells to solve again: failed linear solves (Levenberg retry by the host-driven solver: degenerate information,
         // rare) and borderline cells (the literal trial loop, by the cell kernels themselves over compact per-slot lists).
         // ONE read-back of the counts -- the single host wait of a repeated step.
-        if ((int)total > h->failed_cap) {
-            HIPCHK(hipFree(h->d_failed));
-            h->d_failed = nullptr;
+        if (!h->d_failed || (int)total > h->failed_cap) {
             h->failed_cap = std::max(16384, (int)(total + total / 8));
-            HIPCHK(hipMalloc(&h->d_failed, sizeof(int) * ((size_t)h->failed_cap + 1)));
+            HIPCHK(h->d_failed.alloc((size_t)h->failed_cap + 1));
         }
         HIPCHK(hipMemsetAsync(h->d_recount, 0, sizeof(int) * (NS + 1), st));
         hipLaunchKernelGGL(k_collect_failed, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total, (const int4*)h->d_meta,
@@ -2074,6 +2037,18 @@ extern "C" int ipc_set_max(ipc_engine_t* h, const uint64_t* d_bits, uint8_t* d_a
     return IPC_OK;
 }
 
+// scratch of ipc_run and its relatives: upper triangle, matrix, accepted bytes for N candidates (need = N * words)
+static int ensure_run_scratch(ipc_engine* h, int N, size_t need)
+{
+    if (need <= h->run_cap) return IPC_OK;
+    h->run_cap = 0;                                                // (until all three are there: a failure part way comes here again)
+    HIPCHK(h->d_upper.alloc(need));
+    HIPCHK(h->d_bits.alloc(need));
+    HIPCHK(h->d_acc.alloc((size_t)N + 64));
+    h->run_cap = need;
+    return IPC_OK;
+}
+
 extern "C" int ipc_run(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accepted_out)
 {
     if (!h) return fail(IPC_ERR_ARG, "ipc_run: NULL handle");
@@ -2081,19 +2056,12 @@ extern "C" int ipc_run(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accepted_ou
     HIPCHK(hipSetDevice(h->device));
     const int N = h->N, words = (N + 63) / 64;
     const size_t need = (size_t)N * words;
-    if (need > h->run_cap) {
-        hipFree(h->d_upper); hipFree(h->d_bits); hipFree(h->d_acc);
-        h->d_upper = h->d_bits = nullptr; h->d_acc = nullptr;
-        HIPCHK(hipMalloc(&h->d_upper, sizeof(uint64_t) * need));
-        HIPCHK(hipMalloc(&h->d_bits, sizeof(uint64_t) * need));
-        HIPCHK(hipMalloc(&h->d_acc, (size_t)N + 64));
-        h->run_cap = need;
-    }
-    int rc = ipc_solve_rows(h, 0, 1, (uint64_t*)h->d_upper, h->own_stream);
+    if (int rc = ensure_run_scratch(h, N, need)) return rc;
+    int rc = ipc_solve_rows(h, 0, 1, h->d_upper, h->own_stream);
     if (rc) return rc;
-    rc = ipc_assemble_matrix(h, (const uint64_t*)h->d_upper, 1, (uint64_t*)h->d_bits, h->own_stream);
+    rc = ipc_assemble_matrix(h, h->d_upper, 1, h->d_bits, h->own_stream);
     if (rc) return rc;
-    rc = ipc_set_max(h, (const uint64_t*)h->d_bits, h->d_acc, h->own_stream);
+    rc = ipc_set_max(h, h->d_bits, h->d_acc, h->own_stream);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(h->own_stream));
     if (bits_out) HIPCHK(hipMemcpy(bits_out, h->d_bits, sizeof(uint64_t) * need, hipMemcpyDeviceToHost));
@@ -2110,18 +2078,18 @@ static int grow_online(ipc_engine* h, int cap)
 {
     const int wcap = cap / 64, M = h->on_cov;
     hipStream_t st = h->own_stream;
-    unsigned long long *n_upper = nullptr, *n_bits = nullptr, *n_mask = nullptr;
-    unsigned char* n_acc = nullptr; int* n_live = nullptr;
+    DevBuf<unsigned long long> n_upper, n_bits, n_mask;
+    DevBuf<unsigned char> n_acc; DevBuf<int> n_live;
     const size_t mat = sizeof(unsigned long long) * (size_t)cap * wcap;
     size_t mem_free = 0, mem_total = 0;                  // (quadratic in the capacity: 2 x 512 MB at 65 536 candidates -- refused before anything is allocated)
     HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
     if (2 * mat + 16 * (size_t)cap > mem_free)
         return fail(IPC_ERR_LIMIT, "online matrix for %d candidates needs %zu MB, the device has %zu MB free", cap, (2 * mat) >> 20, mem_free >> 20);
-    HIPCHK(hipMalloc(&n_upper, mat));
-    HIPCHK(hipMalloc(&n_bits, mat));
-    HIPCHK(hipMalloc(&n_mask, sizeof(unsigned long long) * wcap));
-    HIPCHK(hipMalloc(&n_acc, (size_t)cap));
-    HIPCHK(hipMalloc(&n_live, sizeof(int) * ((size_t)cap + 1)));
+    HIPCHK(n_upper.alloc((size_t)cap * wcap));
+    HIPCHK(n_bits.alloc((size_t)cap * wcap));
+    HIPCHK(n_mask.alloc(wcap));
+    HIPCHK(n_acc.alloc(cap));
+    HIPCHK(n_live.alloc((size_t)cap + 1));
     HIPCHK(hipMemsetAsync(n_upper, 0, mat, st));
     HIPCHK(hipMemsetAsync(n_bits, 0, mat, st));
     HIPCHK(hipMemsetAsync(n_mask, 0, sizeof(unsigned long long) * wcap, st));
@@ -2136,9 +2104,9 @@ static int grow_online(ipc_engine* h, int cap)
         HIPCHK(hipMemcpyAsync(n_live, h->d_on_live, sizeof(int) * (size_t)M, hipMemcpyDeviceToDevice, st));
         HIPCHK(hipMemcpyAsync(n_live + cap, h->d_on_live + h->on_ccap, sizeof(int), hipMemcpyDeviceToDevice, st));
     }
-    for (void* q : {(void*)h->d_on_upper, (void*)h->d_on_bits, (void*)h->d_on_mask, (void*)h->d_on_acc, (void*)h->d_on_live})
-        if (q) h->retired.push_back(q);
-    h->d_on_upper = n_upper; h->d_on_bits = n_bits; h->d_on_mask = n_mask; h->d_on_acc = n_acc; h->d_on_live = n_live;
+    retire(h, h->d_on_upper); retire(h, h->d_on_bits); retire(h, h->d_on_mask); retire(h, h->d_on_acc); retire(h, h->d_on_live);
+    h->d_on_upper = std::move(n_upper); h->d_on_bits = std::move(n_bits); h->d_on_mask = std::move(n_mask);
+    h->d_on_acc = std::move(n_acc); h->d_on_live = std::move(n_live);
     h->on_ccap = cap; h->on_wcap = wcap;
     ++h->online_growths;
     return IPC_OK;
@@ -2632,33 +2600,34 @@ static int ensure_incremental(ipc_engine* h, const char* who)
     HIPCHK(hipSetDevice(h->device));
     if (h->dim == 3) {
         if (!h->d_cur) {
-            h->d_open = h->d_pose0;                   // same [12][V] layout; not owned twice, see ipc_destroy
-            HIPCHK(hipMalloc(&h->d_cur, sizeof(double) * (12 * (size_t)h->vcap + kPoseTrail)));
+            h->d_open = h->d_pose0;                   // same [12][V] layout; d_open does not own
+            HIPCHK(h->d_cur.alloc(12 * (size_t)h->vcap + kPoseTrail));
             if (int rc = reset_current(h)) return rc;
         }
         if (!h->cluster3) {
-            h->cluster3 = new ClusterSolver3(); h->cluster3->term_eps = h->term_eps; h->cluster3->allow_damping = h->lm_retry;
+            h->cluster3.reset(new ClusterSolver3()); h->cluster3->term_eps = h->term_eps; h->cluster3->allow_damping = h->lm_retry;
             h->cluster3->literal_band_min_n = h->literal_band_min_n;
         }
         if (!h->persist3) {
-            h->persist3 = new PersistSolver<PersistSe3>(h->knobs); h->persist3->term_eps = h->term_eps; h->persist3->d_prof = h->d_prof;
+            h->persist3.reset(new PersistSolver<PersistSe3>(h->knobs)); h->persist3->term_eps = h->term_eps; h->persist3->d_prof = h->d_prof;
             if (h->max_helpers >= 0) h->persist3->max_helpers = h->max_helpers;
         }
         return IPC_OK;
     }
-    if (!h->d_open) {
-        HIPCHK(hipMalloc(&h->d_open, sizeof(double) * (5 * (size_t)h->vcap + kPoseTrail)));
-        HIPCHK(hipMalloc(&h->d_cur, sizeof(double) * (5 * (size_t)h->vcap + kPoseTrail)));
+    if (!h->d_cur) {
+        HIPCHK(h->d_open_own.alloc(5 * (size_t)h->vcap + kPoseTrail));
+        h->d_open = h->d_open_own;
+        HIPCHK(h->d_cur.alloc(5 * (size_t)h->vcap + kPoseTrail));
         hipLaunchKernelGGL(k_pose5_init, dim3((h->V + 255) / 256), dim3(256), 0, h->own_stream, h->V, h->d_pose0, h->vcap, h->d_open, h->vcap);
         HIPCHK(hipGetLastError());
         if (int rc = reset_current(h)) return rc;
     }
     if (!h->cluster) {
-        h->cluster = new ClusterSolver2(); h->cluster->term_eps = h->term_eps; h->cluster->allow_damping = h->lm_retry;
+        h->cluster.reset(new ClusterSolver2()); h->cluster->term_eps = h->term_eps; h->cluster->allow_damping = h->lm_retry;
         h->cluster->literal_band_min_n = h->literal_band_min_n;
     }
     if (!h->persist2) {
-        h->persist2 = new PersistSolver<PersistSe2>(h->knobs); h->persist2->term_eps = h->term_eps; h->persist2->d_prof = h->d_prof;
+        h->persist2.reset(new PersistSolver<PersistSe2>(h->knobs)); h->persist2->term_eps = h->term_eps; h->persist2->d_prof = h->d_prof;
         if (h->max_helpers >= 0) h->persist2->max_helpers = h->max_helpers;
     }
     return IPC_OK;
@@ -2716,14 +2685,13 @@ extern "C" int ipc_incremental_set_state(ipc_engine_t* h, const double* poses, c
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(h->own_stream));
     } else {
-        double* d_tmp = nullptr;                           // [3][V] -> [5][V] (cos, sin as every pose of the engine carries them)
-        HIPCHK(hipMalloc(&d_tmp, sizeof(double) * 3 * V));
+        DevBuf<double> d_tmp;                              // [3][V] -> [5][V] (cos, sin as every pose of the engine carries them)
+        HIPCHK(d_tmp.alloc(3 * V));
         HIPCHK(hipMemcpyAsync(d_tmp, tmp.data(), sizeof(double) * 3 * V, hipMemcpyHostToDevice, h->own_stream));
         hipLaunchKernelGGL(k_pose5_init, dim3((h->V + 255) / 256), dim3(256), 0, h->own_stream, h->V, d_tmp, h->V, h->d_cur, h->vcap);
         hipLaunchKernelGGL(k_state_D<5>, dim3(1), dim3(64), 0, h->own_stream, h->V, h->vcap, (const double*)h->d_open, h->d_cur);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(h->own_stream));
-        HIPCHK(hipFree(d_tmp));
     }
     h->cns.assign(cns, cns + n_cns);
     h->cns_dups = false;
@@ -2885,10 +2853,10 @@ static int probe_stream_concurrency(hipStream_t* st, int n)
 static int spec_ensure(ipc_engine* h)
 {
     if (!h->slots.empty()) return IPC_OK;
-    HIPCHK(hipHostMalloc(&h->h_abort, sizeof(int) * 64, hipHostMallocMapped));
+    HIPCHK(h->h_abort.alloc(64, hipHostMallocMapped));
     std::memset(h->h_abort, 0, sizeof(int) * 64);
     HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_abort), h->h_abort, 0));
-    HIPCHK(hipEventCreateWithFlags(&h->ev_commit, hipEventDisableTiming));
+    HIPCHK(h->ev_commit.create(hipEventDisableTiming));
     h->slots.resize(h->spec_window);
     h->spec_active = h->spec_window;
     if (h->max_helpers >= 0) h->helper_limit = std::min(h->helper_limit, h->max_helpers);
@@ -2897,13 +2865,13 @@ static int spec_ensure(ipc_engine* h)
     for (int q = 0; q < h->spec_window; ++q) {
         ipc_engine::SpecSlot& sl = h->slots[q];
         HIPCHK(pipeline_stream(h->device, q, &sl.st));
-        HIPCHK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+        HIPCHK(sl.done.create(hipEventDisableTiming));
         if (h->dim == 3) {
-            sl.s3 = new PersistSolver<PersistSe3>(h->knobs); sl.s3->term_eps = h->term_eps; sl.s3->d_prof = q == 0 ? h->d_prof : nullptr;
+            sl.s3.reset(new PersistSolver<PersistSe3>(h->knobs)); sl.s3->term_eps = h->term_eps; sl.s3->d_prof = q == 0 ? h->d_prof : nullptr;
             sl.s3->d_abort_word = h->d_abort + q;
             HIPCHK(sl.s3->reserve(h->vcap - 1, std::max(256, std::min(h->N + 1, 16384)), 256));
         } else {
-            sl.s2 = new PersistSolver<PersistSe2>(h->knobs); sl.s2->term_eps = h->term_eps; sl.s2->d_prof = q == 0 ? h->d_prof : nullptr;
+            sl.s2.reset(new PersistSolver<PersistSe2>(h->knobs)); sl.s2->term_eps = h->term_eps; sl.s2->d_prof = q == 0 ? h->d_prof : nullptr;
             sl.s2->d_abort_word = h->d_abort + q;
             HIPCHK(sl.s2->reserve(h->vcap - 1, std::max(256, std::min(h->N + 1, 16384)), 256));
         }
@@ -2956,9 +2924,10 @@ static int spec_alloc_state(ipc_engine* h, int& idx)
         h->spec_states.emplace_back();
         idx = (int)h->spec_states.size() - 1;
         ipc_engine::SpecState& n = h->spec_states[idx];
-        HIPCHK(hipMalloc(&n.d_poses, sizeof(double) * ((h->dim == 2 ? 5 : 12) * (size_t)h->vcap + kPoseTrail)));
+        HIPCHK(n.own_poses.alloc((h->dim == 2 ? 5 : 12) * (size_t)h->vcap + kPoseTrail));
+        n.d_poses = n.own_poses;
         n.owned = true;
-        HIPCHK(hipEventCreateWithFlags(&n.ready, hipEventDisableTiming));
+        HIPCHK(n.ready.create(hipEventDisableTiming));
     }
     ipc_engine::SpecState& n = h->spec_states[idx];
     n.live = true; n.users = 0; n.pos = -1; n.has_ready = false; n.has_pred = n.pred_ready = false; n.cns.clear();
@@ -3025,15 +2994,13 @@ static int spec_predict_state(ipc_engine* h, int si, hipStream_t st)
     ipc_engine::SpecState& S = h->spec_states[si];
     S.has_pred = S.pred_ready = false;
     if (!(h->pred_k > 0.0) || h->N == 0) return IPC_OK;
-    if (S.pred_cap < h->N) {                       // (candidates appended since: a kernel of the state's last life may still write the old array)
+    if (!S.h_pred || S.pred_cap < h->N) {                   // (candidates appended since: a kernel of the state's last life may still write the old array)
         if (S.h_pred && S.pred_ev) HIPCHK(hipEventSynchronize(S.pred_ev));
-        if (S.h_pred) HIPCHK(hipHostFree(S.h_pred));
-        S.h_pred = nullptr;
         S.pred_cap = std::max(1024, 2 * h->N);
-        HIPCHK(hipHostMalloc(&S.h_pred, sizeof(double) * S.pred_cap, hipHostMallocMapped));
+        HIPCHK(S.h_pred.alloc(S.pred_cap, hipHostMallocMapped));
         HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&S.d_pred), S.h_pred, 0));
     }
-    if (!S.pred_ev) HIPCHK(hipEventCreateWithFlags(&S.pred_ev, hipEventDisableTiming));
+    if (!S.pred_ev) HIPCHK(S.pred_ev.create(hipEventDisableTiming));
     if (h->cand_event) HIPCHK(hipStreamWaitEvent(st, h->ev_cand, 0));
     S.pred_n = h->N;
     if (h->dim == 3)
@@ -3548,31 +3515,32 @@ static int grow_chain(ipc_engine* h, int cap)
     const int nf = h->dim == 2 ? (int)F_NFIELDS : (int)G_NFIELDS, ps = h->dim == 2 ? 3 : 12, NF = h->dim == 2 ? 5 : 12;
     const int E = h->V - 1, ostride = h->estride, ocap = h->vcap, nstride = cap;
     hipStream_t st = h->own_stream;
-    auto retire = [&](void* q) { if (q) h->retired.push_back(q); };
-    auto regrow = [&](double*& arr, size_t ndoubles, int rows, int ncopy, int opitch, int npitch) -> int {
-        double* n = nullptr;
-        HIPCHK(hipMalloc(&n, sizeof(double) * ndoubles));
-        HIPCHK(hipMemsetAsync(n, 0, sizeof(double) * ndoubles, st));
+    auto regrow = [&](auto& arr, size_t count, int rows, size_t ncopy, size_t opitch, size_t npitch) -> int {   // (all in elements of arr)
+        const size_t sz = sizeof(*arr.get());
+        std::remove_reference_t<decltype(arr)> n;
+        HIPCHK(n.alloc(count));
+        HIPCHK(hipMemsetAsync(n, 0, sz * count, st));
         if (ncopy > 0)
-            HIPCHK(hipMemcpy2DAsync(n, sizeof(double) * npitch, arr, sizeof(double) * opitch, sizeof(double) * ncopy, rows, hipMemcpyDeviceToDevice, st));
-        retire(arr);
-        arr = n;
+            HIPCHK(hipMemcpy2DAsync(n, sz * npitch, arr, sz * opitch, sz * ncopy, rows, hipMemcpyDeviceToDevice, st));
+        retire(h, arr);
+        arr = std::move(n);
         return IPC_OK;
     };
     if (int rc = regrow(h->d_chain, nf * (size_t)nstride + 64, nf, E, ostride, nstride)) return rc;
     if (h->d_chain1) { if (int rc = regrow(h->d_chain1, nf * (size_t)nstride + 64, nf, E, ostride, nstride)) return rc; }
     if (int rc = regrow(h->d_chain_rec, (size_t)nf * (nstride + 64), 1, E * nf, E * nf, E * nf)) return rc;
     if (h->dim == 3) {
-        const size_t blk = (size_t)kSe3BlkPairs * 64 * 2;                 // doubles per block of 64 edges
-        double* b = reinterpret_cast<double*>(h->d_chain_blk);
-        const int nold = (E + 63) / 64;
-        if (int rc = regrow(b, blk * ((size_t)nstride / 64 + 2), 1, (int)(blk * nold), (int)(blk * nold), (int)(blk * nold))) return rc;
-        h->d_chain_blk = reinterpret_cast<double2*>(b);
+        const size_t blk = (size_t)kSe3BlkPairs * 64;                     // double2 per block of 64 edges
+        const size_t nold = (E + 63) / 64;
+        if (int rc = regrow(h->d_chain_blk, blk * ((size_t)nstride / 64 + 2), 1, blk * nold, blk * nold, blk * nold)) return rc;
     }
     const bool alias = h->d_open == h->d_pose0;                           // (SE3: one array)
     if (int rc = regrow(h->d_pose0, ps * (size_t)cap, ps, h->V, ocap, cap)) return rc;
     if (alias) h->d_open = h->d_pose0;
-    else if (h->d_open) { if (int rc = regrow(h->d_open, 5 * (size_t)cap + kPoseTrail, 5, h->V, ocap, cap)) return rc; }
+    else if (h->d_open) {
+        if (int rc = regrow(h->d_open_own, 5 * (size_t)cap + kPoseTrail, 5, h->V, ocap, cap)) return rc;
+        h->d_open = h->d_open_own;
+    }
     double* old_cur = h->d_cur;
     if (h->d_cur) {
         if (int rc = regrow(h->d_cur, NF * (size_t)cap + kPoseTrail, NF, h->V, ocap, cap)) return rc;
@@ -3581,9 +3549,10 @@ static int grow_chain(ipc_engine* h, int cap)
     // the pipeline's pose states (none is alive after the quiesce: their contents go) and its workspaces, sized by the chain
     for (auto& S : h->spec_states) {
         if (!S.owned) { S.d_poses = h->d_cur; continue; }
-        retire(S.d_poses);
+        retire(h, S.own_poses);
         S.d_poses = nullptr;
-        HIPCHK(hipMalloc(&S.d_poses, sizeof(double) * (NF * (size_t)cap + kPoseTrail)));
+        HIPCHK(S.own_poses.alloc(NF * (size_t)cap + kPoseTrail));
+        S.d_poses = S.own_poses;
     }
     for (auto& sl : h->slots) {
         if (sl.s3) HIPCHK(sl.s3->reserve(cap - 1, std::max(256, std::min(h->N + 1, 16384)), 256));
@@ -3635,7 +3604,7 @@ extern "C" int ipc_append_odometry(ipc_engine_t* h, int n_edges, const double* m
         if (int rc = grow_chain(h, (int)cap)) return rc;
     }
     hipStream_t st = h->own_stream;
-    if (!h->ev_cand) HIPCHK(hipEventCreateWithFlags(&h->ev_cand, hipEventDisableTiming));
+    if (!h->ev_cand) HIPCHK(h->ev_cand.create(hipEventDisableTiming));
     const ChainPtrs C = chain_ptrs(h);
     const double scale = h->prm.s_factor;
     if (n_edges == 1) {
@@ -3647,15 +3616,12 @@ extern "C" int ipc_append_odometry(ipc_engine_t* h, int n_edges, const double* m
     } else {
         const size_t nd = (size_t)(ms + is) * n_edges;
         if (h->stage_used) HIPCHK(hipEventSynchronize(h->ev_stage));       // (the kernel of the burst before still reads the buffer)
-        if (nd > h->stage_cap) {
-            if (h->h_stage) HIPCHK(hipHostFree(h->h_stage));
-            h->h_stage = nullptr; h->stage_cap = 0;
-            const size_t want = std::max(nd, (size_t)(ms + is) * 1024);
-            HIPCHK(hipHostMalloc(&h->h_stage, sizeof(double) * want, hipHostMallocMapped));
+        if (!h->h_stage || nd > h->stage_cap) {
+            h->stage_cap = std::max(nd, (size_t)(ms + is) * 1024);
+            HIPCHK(h->h_stage.alloc(h->stage_cap, hipHostMallocMapped));
             HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_stage), h->h_stage, 0));
-            h->stage_cap = want;
         }
-        if (!h->ev_stage) HIPCHK(hipEventCreateWithFlags(&h->ev_stage, hipEventDisableTiming));
+        if (!h->ev_stage) HIPCHK(h->ev_stage.create(hipEventDisableTiming));
         std::memcpy(h->h_stage, meas, sizeof(double) * ms * n_edges);
         std::memcpy(h->h_stage + (size_t)ms * n_edges, info, sizeof(double) * is * n_edges);
         const double* dm = h->d_stage;
@@ -3794,26 +3760,25 @@ extern "C" int ipc_final_optimize(ipc_engine_t* h, const uint8_t* accepted, int 
     if (int rc = ensure_incremental(h, "ipc_final_optimize")) return rc;
     const int E = h->V - 1;
     if (!h->d_chain1) {
-        double *d_m = nullptr, *d_i = nullptr;
+        DevBuf<double> chain1, d_m, d_i;                           // (chain1 becomes the engine's once it is complete)
         const int ms = h->dim == 2 ? 3 : 7, is = h->dim == 2 ? 6 : 21;
         const size_t nf = h->dim == 2 ? (size_t)F_NFIELDS : (size_t)G_NFIELDS;
-        HIPCHK(hipMalloc(&h->d_chain1, sizeof(double) * (nf * h->estride + 64)));
-        HIPCHK(hipMalloc(&d_m, sizeof(double) * ms * E));
-        HIPCHK(hipMalloc(&d_i, sizeof(double) * is * E));
+        HIPCHK(chain1.alloc(nf * h->estride + 64));
+        HIPCHK(d_m.alloc((size_t)ms * E));
+        HIPCHK(d_i.alloc((size_t)is * E));
         HIPCHK(hipMemcpy(d_m, h->h_odom_meas.data(), sizeof(double) * ms * E, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(d_i, h->h_odom_info.data(), sizeof(double) * is * E, hipMemcpyHostToDevice));
         HIPCHK(hipStreamSynchronize(nullptr));                     // (NULL-stream copies are not ordered against the engine's non-blocking streams: copy_d2d_now)
-        HIPCHK(hipMemsetAsync(h->d_chain1, 0, sizeof(double) * (nf * h->estride + 64), h->own_stream));
+        HIPCHK(hipMemsetAsync(chain1, 0, sizeof(double) * (nf * h->estride + 64), h->own_stream));
         if (h->dim == 2)
             hipLaunchKernelGGL(k_se2_prep, dim3((E + 255) / 256), dim3(256), 0, h->own_stream, E, d_m, d_i,
-                               h->prm.s_factor, h->d_chain1, h->estride, h->prm.s_factor);
+                               h->prm.s_factor, chain1, h->estride, h->prm.s_factor);
         else
             hipLaunchKernelGGL(k_se3_prep, dim3((E + 63) / 64), dim3(64), 0, h->own_stream, E, d_m, d_i,
-                               h->prm.s_factor, h->d_chain1, h->estride, h->prm.s_factor);
+                               h->prm.s_factor, chain1, h->estride, h->prm.s_factor);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(h->own_stream));
-        HIPCHK(hipFree(d_m));
-        HIPCHK(hipFree(d_i));
+        h->d_chain1 = std::move(chain1);
     }
     std::vector<int> members;
     for (int k : h->order) if (accepted[k]) members.push_back(k);
@@ -3848,14 +3813,14 @@ extern "C" int ipc_debug_dense_solve(int n, const double* system, int mode, int 
 {
     if (n < 1 || !system || !x_out || !info_out) return fail(IPC_ERR_ARG, "ipc_debug_dense_solve: bad argument");
     const size_t m = (size_t)(n + 1) * n;
-    double *dA = nullptr, *dx = nullptr, *ddinv = nullptr;
-    int* dinfo = nullptr;
-    PersistCtl* dctl = nullptr;
-    HIPCHK(hipMalloc(&dA, sizeof(double) * 2 * m));
-    HIPCHK(hipMalloc(&dx, sizeof(double) * (n + 64)));
-    HIPCHK(hipMalloc(&ddinv, sizeof(double) * (n + 64)));
-    HIPCHK(hipMalloc(&dinfo, sizeof(int)));
-    HIPCHK(hipMalloc(&dctl, sizeof(PersistCtl)));
+    DevBuf<double> dA, dx, ddinv;
+    DevBuf<int> dinfo;
+    DevBuf<PersistCtl> dctl;
+    HIPCHK(dA.alloc(2 * m));
+    HIPCHK(dx.alloc(n + 64));
+    HIPCHK(ddinv.alloc(n + 64));
+    HIPCHK(dinfo.alloc(1));
+    HIPCHK(dctl.alloc(1));
     HIPCHK(hipMemcpy(dA, system, sizeof(double) * m, hipMemcpyHostToDevice));
     HIPCHK(hipMemset(dA + m, 0, sizeof(double) * m));
     HIPCHK(hipMemset(dinfo, 0, sizeof(int)));
@@ -3874,7 +3839,6 @@ extern "C" int ipc_debug_dense_solve(int n, const double* system, int mode, int 
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(x_out, dx, sizeof(double) * n, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(info_out, dinfo, sizeof(int), hipMemcpyDeviceToHost));
-    hipFree(dA); hipFree(dx); hipFree(ddinv); hipFree(dinfo); hipFree(dctl);
     return IPC_OK;
 }
 
@@ -3889,14 +3853,14 @@ extern "C" int ipc_debug_band_solve(int nb, int m, int W, const double* system, 
     B.nb = nb; B.m = m; B.W = W; B.ldb = W + m; B.n = nb + m - 1;
     if (B.n < 1) return fail(IPC_ERR_ARG, "ipc_debug_band_solve: empty system");
     const size_t sz = B.doubles();
-    double *dA = nullptr, *dx = nullptr, *ddinv = nullptr;
-    int* dinfo = nullptr;
-    PersistCtl* dctl = nullptr;
-    HIPCHK(hipMalloc(&dA, sizeof(double) * 2 * sz));
-    HIPCHK(hipMalloc(&dx, sizeof(double) * (B.n + 64)));
-    HIPCHK(hipMalloc(&ddinv, sizeof(double) * (B.n + 64)));
-    HIPCHK(hipMalloc(&dinfo, sizeof(int)));
-    HIPCHK(hipMalloc(&dctl, sizeof(PersistCtl)));
+    DevBuf<double> dA, dx, ddinv;
+    DevBuf<int> dinfo;
+    DevBuf<PersistCtl> dctl;
+    HIPCHK(dA.alloc(2 * sz));
+    HIPCHK(dx.alloc(B.n + 64));
+    HIPCHK(ddinv.alloc(B.n + 64));
+    HIPCHK(dinfo.alloc(1));
+    HIPCHK(dctl.alloc(1));
     HIPCHK(hipMemset(dA, 0, sizeof(double) * 2 * sz));
     HIPCHK(hipMemcpy(dA, system, sizeof(double) * (size_t)B.n * B.ldb, hipMemcpyHostToDevice));
     HIPCHK(hipMemset(dinfo, 0, sizeof(int)));
@@ -3911,12 +3875,12 @@ extern "C" int ipc_debug_band_solve(int nb, int m, int W, const double* system, 
     HIPCHK(hipDeviceSynchronize());
     if (const char* reps_env = getenv("IPC_BAND_SOLVE_REPS")) {          // (tuning: the factorisation + back substitution alone, timed)
         const int reps = std::max(1, atoi(reps_env));
-        double* dA0 = nullptr;
-        HIPCHK(hipMalloc(&dA0, sizeof(double) * sz));
+        DevBuf<double> dA0;
+        HIPCHK(dA0.alloc(sz));
         HIPCHK(hipMemset(dA0, 0, sizeof(double) * sz));
         HIPCHK(hipMemcpy(dA0, system, sizeof(double) * (size_t)B.n * B.ldb, hipMemcpyHostToDevice));
-        hipEvent_t e0, e1;
-        HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+        Event e0, e1;
+        HIPCHK(e0.create()); HIPCHK(e1.create());
         float total_ms = 0.f;
         for (int r = 0; r < reps; ++r) {
             HIPCHK(hipMemcpyAsync(dA, dA0, sizeof(double) * sz, hipMemcpyDeviceToDevice, nullptr));
@@ -3931,11 +3895,16 @@ extern "C" int ipc_debug_band_solve(int nb, int m, int W, const double* system, 
         }
         fprintf(stderr, "[band solve] n %d W %d m %d workgroups %d: %.1f us per factorisation + back substitution (%d block columns, %.2f us each)\n",
                 B.n, B.W, B.m, workgroups, 1e3 * total_ms / reps, (B.n + kCB - 1) / kCB, 1e3 * total_ms / reps / ((B.n + kCB - 1) / kCB));
-        hipEventDestroy(e0); hipEventDestroy(e1); hipFree(dA0);
     }
     HIPCHK(hipMemcpy(x_out, dx, sizeof(double) * B.n, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(info_out, dinfo, sizeof(int), hipMemcpyDeviceToHost));
-    hipFree(dA); hipFree(dx); hipFree(ddinv); hipFree(dinfo); hipFree(dctl);
+    return IPC_OK;
+}
+
+extern "C" int ipc_debug_live_resources(int out[3])
+{
+    if (!out) return fail(IPC_ERR_ARG, "ipc_debug_live_resources: out is NULL");
+    out[0] = g_live_devbufs.load(); out[1] = g_live_pinned.load(); out[2] = g_live_events.load();
     return IPC_OK;
 }
 
@@ -3964,19 +3933,12 @@ extern "C" int ipc_run_set_only(ipc_engine_t* h, uint8_t* accepted_out, int* sol
     HIPCHK(hipSetDevice(h->device));
     const int N = h->N, words = (N + 63) / 64;
     const size_t need = (size_t)N * words;
-    if (need > h->run_cap) {
-        hipFree(h->d_upper); hipFree(h->d_bits); hipFree(h->d_acc);
-        h->d_upper = h->d_bits = nullptr; h->d_acc = nullptr;
-        HIPCHK(hipMalloc(&h->d_upper, sizeof(uint64_t) * need));
-        HIPCHK(hipMalloc(&h->d_bits, sizeof(uint64_t) * need));
-        HIPCHK(hipMalloc(&h->d_acc, (size_t)N + 64));
-        h->run_cap = need;
-    }
-    int rc = solve_rows_impl(h, 0, 1, (uint64_t*)h->d_upper, h->own_stream, 1);
+    if (int rc = ensure_run_scratch(h, N, need)) return rc;
+    int rc = solve_rows_impl(h, 0, 1, h->d_upper, h->own_stream, 1);
     const int diag_cells = h->last_cells;
-    if (!rc) rc = solve_rows_impl(h, 0, 1, (uint64_t*)h->d_upper, h->own_stream, 2);
-    if (!rc) rc = ipc_assemble_matrix(h, (const uint64_t*)h->d_upper, 1, (uint64_t*)h->d_bits, h->own_stream);
-    if (!rc) rc = ipc_set_max(h, (const uint64_t*)h->d_bits, h->d_acc, h->own_stream);
+    if (!rc) rc = solve_rows_impl(h, 0, 1, h->d_upper, h->own_stream, 2);
+    if (!rc) rc = ipc_assemble_matrix(h, h->d_upper, 1, h->d_bits, h->own_stream);
+    if (!rc) rc = ipc_set_max(h, h->d_bits, h->d_acc, h->own_stream);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(h->own_stream));
     if (solved_cells_out) *solved_cells_out = diag_cells + h->last_cells;
@@ -4004,16 +3966,9 @@ extern "C" int ipc_run_sharded(ipc_engine_t** engines, int n_engines, uint64_t* 
     const int N = h0->N, words = (N + 63) / 64, world = n_engines, rpr = ipc_rows_per_rank(N, world);
     const size_t shard = (size_t)rpr * words, need = (size_t)N * words;
     HIPCHK(hipSetDevice(h0->device));
-    if (need > h0->run_cap) {
-        hipFree(h0->d_upper); hipFree(h0->d_bits); hipFree(h0->d_acc);
-        h0->d_upper = h0->d_bits = nullptr; h0->d_acc = nullptr;
-        HIPCHK(hipMalloc(&h0->d_upper, sizeof(uint64_t) * need));
-        HIPCHK(hipMalloc(&h0->d_bits, sizeof(uint64_t) * need));
-        HIPCHK(hipMalloc(&h0->d_acc, (size_t)N + 64));
-        h0->run_cap = need;
-    }
-    unsigned long long* d_gathered = nullptr;
-    HIPCHK(hipMalloc(&d_gathered, sizeof(uint64_t) * shard * world));
+    if (int rc = ensure_run_scratch(h0, N, need)) return rc;
+    DevBuf<uint64_t> d_gathered;
+    HIPCHK(d_gathered.alloc(shard * world));
     std::vector<int> rcs(world, IPC_OK);
     std::vector<std::string> errs(world);
     std::vector<std::thread> workers;
@@ -4026,25 +3981,24 @@ extern "C" int ipc_run_sharded(ipc_engine_t** engines, int n_engines, uint64_t* 
                 return true;
             };
             if (bad(hipSetDevice(h->device), "hipSetDevice")) return;
-            unsigned long long* d_shard = nullptr;
-            if (bad(hipMalloc(&d_shard, sizeof(uint64_t) * shard), "hipMalloc shard")) return;
-            const int rc = ipc_solve_rows(h, r, world, (uint64_t*)d_shard, h->own_stream);
-            if (rc) { rcs[r] = rc; errs[r] = ipc_last_error(); hipFree(d_shard); return; }
+            DevBuf<uint64_t> d_shard;                          // (freed by this thread, on this device)
+            if (bad(d_shard.alloc(shard), "hipMalloc shard")) return;
+            const int rc = ipc_solve_rows(h, r, world, d_shard, h->own_stream);
+            if (rc) { rcs[r] = rc; errs[r] = ipc_last_error(); return; }
             if (!bad(hipMemcpyPeerAsync(d_gathered + (size_t)r * shard, h0->device, d_shard, h->device, sizeof(uint64_t) * shard, h->own_stream),
                      "hipMemcpyPeerAsync"))
                 bad(hipStreamSynchronize(h->own_stream), "hipStreamSynchronize");
-            hipFree(d_shard);
         });
     }
     for (auto& w : workers) w.join();
     HIPCHK(hipSetDevice(h0->device));
     for (int r = 0; r < world; ++r)
-        if (rcs[r]) { hipFree(d_gathered); return fail((ipc_status)rcs[r], "ipc_run_sharded: rank %d: %s", r, errs[r].c_str()); }
-    int rc = ipc_assemble_matrix(h0, (const uint64_t*)d_gathered, world, (uint64_t*)h0->d_bits, h0->own_stream);
-    if (!rc) rc = ipc_set_max(h0, (const uint64_t*)h0->d_bits, h0->d_acc, h0->own_stream);
-    if (rc) { hipFree(d_gathered); return rc; }
+        if (rcs[r]) return fail((ipc_status)rcs[r], "ipc_run_sharded: rank %d: %s", r, errs[r].c_str());
+    int rc = ipc_assemble_matrix(h0, d_gathered, world, h0->d_bits, h0->own_stream);
+    if (!rc) rc = ipc_set_max(h0, h0->d_bits, h0->d_acc, h0->own_stream);
+    if (rc) return rc;
     HIPCHK(hipStreamSynchronize(h0->own_stream));
-    HIPCHK(hipFree(d_gathered));
+    d_gathered.reset();
     if (bits_out) HIPCHK(hipMemcpy(bits_out, h0->d_bits, sizeof(uint64_t) * need, hipMemcpyDeviceToHost));
     if (accepted_out) HIPCHK(hipMemcpy(accepted_out, h0->d_acc, (size_t)N, hipMemcpyDeviceToHost));
     return IPC_OK;
