@@ -260,7 +260,49 @@ int ipc_online_covered(ipc_engine_t* h, int* m);
 int ipc_online_reset(ipc_engine_t* h);
 int ipc_reserve_candidates(ipc_engine_t* h, int capacity);
 
-/* Diagnostics of the last ipc_solve_rows() or ipc_run_online(): number of solved cells, and their records. */
+/* ---- threshold sweep --------------------------------------------------------------------------------
+ * The reference optimises a cell first and compares afterwards (isAgreeingWithCurrentState, src/consensus_utils.cpp:7-22: the
+ * thresholds enter in :17-19 alone), and its harness reports precision / recall per threshold pair (src/simulation.cpp:70-105):
+ * every new (fast_reject_th, slow_reject_th) costs it a whole run.  ipc_run_sweep stands in for n_th such runs: every cell is
+ * solved ONCE, then the matrix and the consistent set are produced for each pair -- device resident, in chunks of as many
+ * pairs as fit a quarter of the free device memory (IPC_SWEEP_CHUNK=<n>, read at ipc_create, caps the chunk).
+ *
+ * Contract: entry t of bits_out ([n_th][N][ceil(N/64)]) / accepted_out ([n_th][N]) equals, bit for bit, the output of ipc_run
+ * on an engine of the same graph and candidate list whose ipc_params_t differs from this engine's only in fast_reject_th =
+ * fast_th[t] and slow_reject_th = slow_th[t], under the same environment (IPC_TERMINATE_EPS, IPC_BORDERLINE_BAND,
+ * IPC_LM_RETRY, the default kernel policies).  The iteration bases and s_factor are the engine's own (they change the solve:
+ * not sweepable); the engine's own thresholds are not consulted.  Pairs may be unsorted, may repeat, fast > slow is allowed;
+ * any non-NaN double is taken as ipc_create takes it.  One engine, world 1; the N limit of ipc_set_max applies
+ * (IPC_ERR_LIMIT).  The bit-for-bit claim rests on one fact: with the default policies a cell's kernel variant depends on its
+ * bin alone, so a cell's record does not depend on which call solved it.
+ *
+ * The rule per cell (i, j) and pair t, th = (i == j) ? fast_th[t] : slow_th[t], exactly a fresh engine's: a cell whose first
+ * pass ended with flags & 2 takes the Levenberg retry's chi2 (IPC_LM_RETRY on; no band test); else a cell within the
+ * borderline band of th (fabs(chi2 - th) <= band * th, band = 0 with IPC_TERMINATE_EPS=0) takes the chi2 of g2o's literal
+ * loop; else the first pass's chi2; the bit is !(chi2 > th).  The engine keeps the first pass AND the literal records (a cell
+ * can be borderline at one pair and not at another), apart from the arrays ipc_run / ipc_solve_rows / ipc_run_online share:
+ * those calls and the sweep do not disturb each other.  The literal loop runs once more only for the cells that some pair of
+ * the call makes borderline and whose record is not held yet.
+ *
+ * The first pass is held: another ipc_run_sweep on the same candidate list skips it (reused_solve).  ipc_set_candidates,
+ * ipc_append_candidate and ipc_sweep_reset drop it; ipc_append_odometry does not (no existing cell reads a later vertex).
+ * After a sweep ipc_cell_count / ipc_cell_info / ipc_solve_report describe the FIRST-PASS records; literal re-solves appear
+ * only as counts in the report.  The online matrix is neither read nor changed.  bits_out, accepted_out, report may be NULL.
+ * Errors: n_th < 1, fast_th or slow_th NULL, a NaN threshold: IPC_ERR_ARG; no candidates set: IPC_ERR_STATE. */
+typedef struct {
+    int thresholds;        /* T of this call                                                                             */
+    int cells;             /* cells of the first pass (0 when reused_solve)                                              */
+    int long_cells, damped_cells;   /* as in ipc_solve_report_t, of the held first pass                                  */
+    int literal_cells;     /* cells solved again by the literal loop in THIS call (the union over the T pairs, minus those an earlier sweep already holds) */
+    int literal_held;      /* cells whose literal record the engine holds after the call                                 */
+    int reused_solve;      /* 1: the first pass of an earlier ipc_run_sweep on the same candidate list was used          */
+    int chunks;            /* groups of thresholds that went through assemble / set-max together                         */
+} ipc_sweep_report_t;
+int ipc_run_sweep(ipc_engine_t* h, int n_th, const double* fast_th, const double* slow_th, uint64_t* bits_out,
+                  uint8_t* accepted_out, ipc_sweep_report_t* report);
+int ipc_sweep_reset(ipc_engine_t* h);      /* forget the held first pass */
+
+/* Diagnostics of the last ipc_solve_rows(), ipc_run_online() or ipc_run_sweep(): number of solved cells, and their records. */
 int ipc_cell_count(ipc_engine_t* h, int* n_cells);
 int ipc_cell_info(ipc_engine_t* h, ipc_cell_info_t* out, int capacity);
 

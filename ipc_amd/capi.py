@@ -35,6 +35,7 @@ SYMBOLS = [
     "ipc_debug_dense_solve", "ipc_debug_band_solve", "ipc_debug_band_plan", "ipc_debug_absorbed_edges", "ipc_append_candidate", "ipc_incremental_set_state", "ipc_incremental_counters", "ipc_row_assignment", "ipc_run_sharded", "ipc_run_set_only",
     "ipc_append_odometry", "ipc_reserve_vertices", "ipc_vertex_count",
     "ipc_run_online", "ipc_online_covered", "ipc_online_reset", "ipc_reserve_candidates", "ipc_debug_live_resources",
+    "ipc_run_sweep", "ipc_sweep_reset",
 ]
 
 
@@ -69,6 +70,11 @@ class SolveReport(C.Structure):
 class OnlineReport(C.Structure):
     _fields_ = [("covered_before", C.c_int), ("covered_after", C.c_int), ("cells", C.c_int), ("long_cells", C.c_int),
                 ("literal_cells", C.c_int), ("damped_cells", C.c_int), ("set_max_resumed", C.c_int), ("grew", C.c_int)]
+
+
+class SweepReport(C.Structure):
+    _fields_ = [("thresholds", C.c_int), ("cells", C.c_int), ("long_cells", C.c_int), ("damped_cells", C.c_int),
+                ("literal_cells", C.c_int), ("literal_held", C.c_int), ("reused_solve", C.c_int), ("chunks", C.c_int)]
 
 
 CELL_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("lo", "<i4"), ("hi", "<i4"), ("max_chi2", "<f8"),
@@ -119,6 +125,8 @@ def load():
     lib.ipc_online_covered.argtypes = [vp, C.POINTER(ip)]
     lib.ipc_online_reset.argtypes = [vp]
     lib.ipc_reserve_candidates.argtypes = [vp, ip]
+    lib.ipc_run_sweep.argtypes = [vp, ip, vp, vp, vp, vp, C.POINTER(SweepReport)]
+    lib.ipc_sweep_reset.argtypes = [vp]
     lib.ipc_run_sharded.argtypes = [C.POINTER(vp), ip, vp, vp]
     lib.ipc_run_set_only.argtypes = [vp, vp, C.POINTER(ip)]
     lib.ipc_cell_count.argtypes = [vp, C.POINTER(ip)]

@@ -156,6 +156,26 @@ class IPC:
         """Room for n candidates up front, in the candidate arrays and the online matrix (ipc_reserve_candidates)."""
         capi.check(self.lib.ipc_reserve_candidates(self.h, int(n)))
 
+    # ---- threshold sweep: the cells solved once, decided at many (fast_reject_th, slow_reject_th) pairs ----
+    def run_sweep(self, fast_ths, slow_ths, want_bits=False):
+        """ipc_run_sweep: entry t is what run() returns on an engine created with fast_reject_th = fast_ths[t] and
+        slow_reject_th = slow_ths[t] (everything else this engine's).  Returns (accepted [T, N] uint8, report dict), or
+        (bits [T, N, words] uint64, accepted, report) with want_bits.  A sweep has no single set: getMaxConsensusSet()
+        is left as it was."""
+        fast, slow = _d(fast_ths).reshape(-1), _d(slow_ths).reshape(-1)
+        assert fast.shape == slow.shape
+        T = int(fast.shape[0])
+        acc = np.zeros((T, self.N), dtype=np.uint8)
+        bits = np.zeros((T, self.N, self.words), dtype=np.uint64) if want_bits else None
+        r = capi.SweepReport()
+        capi.check(self.lib.ipc_run_sweep(self.h, T, _p(fast), _p(slow), _p(bits) if want_bits else None, _p(acc), C.byref(r)))
+        report = {k: getattr(r, k) for k, _ in capi.SweepReport._fields_}
+        return (bits, acc, report) if want_bits else (acc, report)
+
+    def sweep_reset(self):
+        """Forget the sweep's held first pass (ipc_sweep_reset): the next run_sweep solves every cell."""
+        capi.check(self.lib.ipc_sweep_reset(self.h))
+
     def consistency_matrix(self):
         bits, _ = self.run()
         return unpack_bits(bits, self.N)

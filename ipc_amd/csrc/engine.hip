@@ -434,8 +434,9 @@ __global__ __launch_bounds__(256) void k_assemble(int N, int words, const int* s
 // old row holds at an old column is neither recomputed nor written.  The rule, the one compare per lane and the ballot are
 // those of k_assemble; `upper` and `bits` are [.][stride] words with the identity row map.  A block owns word w: a word with
 // new columns visits every row tile, any other word the tiles that hold new rows.
-__global__ __launch_bounds__(256) void k_assemble_delta(int N, int M, int stride, const int* lo, const int* hi,
-                                                        const unsigned long long* upper, unsigned long long* bits)
+// (The body is a device function: k_sweep_assemble, sweep_kernels.hpp, runs it with M = 0 once per threshold.)
+__device__ __forceinline__ void assemble_tiles(int N, int M, int stride, const int* lo, const int* hi,
+                                               const unsigned long long* upper, unsigned long long* bits)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int w = blockIdx.x;
@@ -477,6 +478,11 @@ __global__ __launch_bounds__(256) void k_assemble_delta(int N, int M, int stride
         }
     }
 }
+__global__ __launch_bounds__(256) void k_assemble_delta(int N, int M, int stride, const int* lo, const int* hi,
+                                                        const unsigned long long* upper, unsigned long long* bits)
+{
+    assemble_tiles(N, M, stride, lo, hi, upper, bits);
+}
 
 // Greedy set-max: candidates in processing order, 64 per round (four per wave -- 32 / two until round 5: a round is two
 // trips to memory whatever it holds, and at N = 25 000 the 160 rounds were 1.3 ms that no rank of an 8-GPU run can shed;
@@ -489,9 +495,10 @@ __global__ __launch_bounds__(256) void k_assemble_delta(int N, int M, int stride
 // call with first > 0 starts from them -- the candidates at the positions first .. N-1 of the order are compacted behind the
 // stored live list and tested, in order, against the stored set and against each other, exactly as the rounds of a whole run
 // reach them (the greedy's verdict on a candidate reads the verdicts in front of it only).
-__global__ __launch_bounds__(1024) void k_set_max(int N, int words, int stride, const int* order,
-                                                  const unsigned long long* bits, unsigned char* accepted, int* live,
-                                                  int first = 0, unsigned long long* mask = nullptr, int* nlive_io = nullptr)
+// (The body is a device function: k_sweep_set_max, sweep_kernels.hpp, runs it once per threshold, one workgroup each.)
+__device__ __forceinline__ void set_max_rounds(int N, int words, int stride, const int* order,
+                                               const unsigned long long* bits, unsigned char* accepted, int* live,
+                                               int first, unsigned long long* mask, int* nlive_io)
 {
     constexpr int CPW = 4, RC = 16 * CPW;           // candidates per wave / per round
     extern __shared__ unsigned long long acc[];     // [words] accepted mask
@@ -575,6 +582,12 @@ __global__ __launch_bounds__(1024) void k_set_max(int N, int words, int stride, 
         for (int w = tid; w < words; w += blockDim.x) mask[w] = acc[w];
         if (tid == 0) *nlive_io = nlive;
     }
+}
+__global__ __launch_bounds__(1024) void k_set_max(int N, int words, int stride, const int* order,
+                                                  const unsigned long long* bits, unsigned char* accepted, int* live,
+                                                  int first = 0, unsigned long long* mask = nullptr, int* nlive_io = nullptr)
+{
+    set_max_rounds(N, words, stride, order, bits, accepted, live, first, mask, nlive_io);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -766,6 +779,21 @@ struct ipc_engine {
     DevBuf<unsigned char> d_on_acc;                                     // [on_ccap] accepted bytes
     DevBuf<int> d_on_live;                                              // [on_ccap + 1] compacted live list, [on_ccap] = its length
     long online_growths = 0;
+    // Threshold sweep (ipc_run_sweep): the first pass over all cells is held apart from d_cells & co., which
+    // ipc_run, ipc_solve_rows and ipc_run_online share -- the cell list, chi0 / chitot / meta (a failed cell's: the Levenberg
+    // retry's), the literal chi2 with its flag word (sweep_kernels.hpp) and the plan's slot offsets and counts.
+    bool sw_valid = false;                             // a first pass of the candidate list of the moment is held
+    bool info_from_sweep = false;                      // ipc_cell_info reads the held first pass (the last matrix call was a sweep)
+    size_t sw_total = 0, sw_cap = 0;                   // cells held / capacity of the six arrays below
+    int sw_long = 0, sw_damped = 0, sw_held = 0;       // long and damped cells of the held pass; literal records held
+    DevBuf<int2> d_sw_cells; DevBuf<double> d_sw_chi, d_sw_chitot, d_sw_lit; DevBuf<int4> d_sw_meta; DevBuf<int> d_sw_flags;
+    DevBuf<unsigned> d_sw_slot_off;                    // [slots + 1]
+    std::vector<unsigned> sw_counts, sw_offsets;
+    DevBuf<double> d_sw_th; int sw_th_cap = 0;         // [fast 0 .. T-1][slow 0 .. T-1] of the call
+    // per-chunk scratch: TC upper triangles and matrices ([t][N][words]), accepted bytes and live lists ([t][N])
+    DevBuf<unsigned long long> d_sw_upper, d_sw_bits; DevBuf<unsigned char> d_sw_acc; DevBuf<int> d_sw_live;
+    size_t sw_mat_cap = 0, sw_vec_cap = 0;             // capacity in words per matrix array / in entries per vector array
+    int sweep_chunk = 0;                               // IPC_SWEEP_CHUNK: cap on the thresholds per chunk (0: none)
     // incremental mode / final map (SE2)
     std::vector<double> h_odom_meas, h_odom_info;      // file values, for the un-scaled chain
     std::vector<int> h_from, h_to, cns;
@@ -1068,6 +1096,7 @@ extern "C" int ipc_create(int dim, int n_vertices, const double* odom_meas, cons
                 return fail(IPC_ERR_ARG, "IPC_BORDERLINE_BAND must be a number in [0, 0.5]");
         }
     }
+    if (const char* sc = getenv("IPC_SWEEP_CHUNK")) { if (*sc) h->sweep_chunk = std::max(0, atoi(sc)); }
     if (const char* sf = getenv("IPC_SLOW_FIRST")) { if (*sf) h->slow_first_iterations = std::max(0, atoi(sf)); }
     if (const char* rb = getenv("IPC_ROW_BALANCE")) {
         if (!strcmp(rb, "cyclic")) h->row_policy = 0;
@@ -1177,6 +1206,7 @@ static void free_candidates(ipc_engine* h)
     h->retired.clear();
     h->N = 0; h->cstride = 0; h->order_stale = false; h->cand_event = false;
     h->on_cov = 0;                                       // (the online matrix's storage stays; its content is that of another list)
+    h->sw_valid = h->info_from_sweep = false;            // (and so does the sweep's: its first pass is that of another list)
 }
 
 // candidate arrays for `cap` records (cap a multiple of 64); the record array zeroed on own_stream
@@ -1385,6 +1415,7 @@ extern "C" int ipc_append_candidate(ipc_engine_t* h, const int* ids, const doubl
     h->N = k + 1;
     h->order_stale = true;
     h->last_cells = 0;                                   // the cells of the last matrix solve are those of the shorter list
+    h->sw_valid = h->info_from_sweep = false;            // ... and so is the sweep's held first pass
     h->plan_cached = false;
     h->ev_valid = false;
     retire(h, h->d_slot);
@@ -1609,6 +1640,7 @@ __device__ __forceinline__ int slot_of_cell(const unsigned* slot_off, int nslots
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (slot_off[mid] <= (unsigned)c) lo = mid; else hi = mid; }
     return lo;
 }
+#include "sweep_kernels.hpp"
 // Failed cells -> list (host-driven Levenberg retry, rare); borderline cells -> the compact list of their slot (lit_cells /
 // lit_idx at the slot's own offset: a slot has room for all of its cells), counted per slot in recount[0 .. nslots).
 __global__ void k_collect_failed(int ncells, const int4* meta, const double* chi, const int2* cells, double fast_th,
@@ -1700,6 +1732,35 @@ __global__ void k_scatter_literal(int ncells, const unsigned* slot_off, int nslo
     const int c = lit_idx[t];
     chi[c] = lit_chi[t]; chitot[c] = lit_chitot[t]; meta[c] = lit_meta[t];
 }
+// One cell (i, j) through the host-driven cluster solver: the check of solve_long_cells (open-loop start, fast / slow iteration
+// base), with Levenberg damping (`damped`: the retry of a failed linear solve) or as g2o's literal trial loop (`literal`: the
+// convergence test off).  The one place both resolve_failed_cells and the sweep's long borderline cells go through.
+static int host_cell_solve(ipc_engine* h, int2 cell, bool damped, bool literal, ClusterOut& o)
+{
+    const int i = cell.x, j = cell.y, nl = i == j ? 1 : 2;
+    const int lo = std::min(h->h_lo[i], h->h_lo[j]), hi = std::max(h->h_hi[i], h->h_hi[j]);
+    std::vector<int> members{i};
+    if (nl == 2) members.push_back(j);
+    int iters = nl == 1 ? h->prm.fast_reject_iter_base : h->prm.slow_reject_iter_base;
+    if ((hi - lo) + nl > 100) iters *= 5;                                  // consensus_utils.cpp:12-13
+    if (damped) {
+        HIPCHK(cluster_solve(h, h->d_chain, h->d_open, lo, hi, members, iters, o, true));    // (damping: host-driven solver)
+        return IPC_OK;
+    }
+    const double te = h->term_eps;
+    auto set_eps = [&](double v) {
+        if (h->cluster) h->cluster->term_eps = v;
+        if (h->cluster3) h->cluster3->term_eps = v;
+        if (h->persist2) h->persist2->term_eps = v;
+        if (h->persist3) h->persist3->term_eps = v;
+    };
+    if (literal) set_eps(0.0);
+    const hipError_t e = cluster_solve(h, h->d_chain, h->d_open, lo, hi, members, iters, o);
+    if (literal) set_eps(te);
+    HIPCHK(e);
+    return IPC_OK;
+}
+
 static int resolve_failed_cells(ipc_engine* h, int n)
 {
     h->last_lm_cells = 0;
@@ -1712,31 +1773,15 @@ static int resolve_failed_cells(ipc_engine* h, int n)
     for (int q = 0; q < n; ++q) {
         int2 cell;
         HIPCHK(hipMemcpy(&cell, h->d_cells + idx[q], sizeof(int2), hipMemcpyDeviceToHost));
-        const int i = cell.x, j = cell.y, nl = i == j ? 1 : 2;
-        const int lo = std::min(h->h_lo[i], h->h_lo[j]), hi = std::max(h->h_hi[i], h->h_hi[j]);
-        std::vector<int> members{i};
-        if (nl == 2) members.push_back(j);
-        int iters = nl == 1 ? h->prm.fast_reject_iter_base : h->prm.slow_reject_iter_base;
-        if ((hi - lo) + nl > 100) iters *= 5;                                  // consensus_utils.cpp:12-13
         ClusterOut o;
         int4 was;
         HIPCHK(hipMemcpy(&was, h->d_meta + idx[q], sizeof(int4), hipMemcpyDeviceToHost));
         if (was.z & 2) {
-            HIPCHK(cluster_solve(h, h->d_chain, h->d_open, lo, hi, members, iters, o, true));    // (damping: host-driven solver)
+            if (int rc = host_cell_solve(h, cell, true, false, o)) return rc;
             ++h->last_lm_cells;
         } else {
             // a borderline cell of the long slots (k_collect_failed): g2o's literal trial loop, convergence test off
-            const double te = h->term_eps;
-            auto set_eps = [&](double v) {
-                if (h->cluster) h->cluster->term_eps = v;
-                if (h->cluster3) h->cluster3->term_eps = v;
-                if (h->persist2) h->persist2->term_eps = v;
-                if (h->persist3) h->persist3->term_eps = v;
-            };
-            set_eps(0.0);
-            const hipError_t e = cluster_solve(h, h->d_chain, h->d_open, lo, hi, members, iters, o);
-            set_eps(te);
-            HIPCHK(e);
+            if (int rc = host_cell_solve(h, cell, false, true, o)) return rc;
             ++h->last_literal_cells;
         }
         const int4 meta = make_int4(o.iterations, o.tries, o.flags, o.evals);
@@ -1823,25 +1868,17 @@ extern "C" int ipc_solve_rows(ipc_engine_t* h, int rank, int world, uint64_t* d_
     return solve_rows_impl(h, rank, world, d_upper, stream, 0);
 }
 
-// "Solve these planned lists": the bin launches over the engine's streams (fork / join around `st`), the cluster solver for
-// chains beyond every cell kernel, the collection of failed and borderline cells with its read-back, the literal re-solve and
-// the host-driven Levenberg retry.  One code path for the batch step (solve_rows_impl) and the online update
-// (ipc_run_online); the results are left in d_chi / d_chitot / d_meta beside d_cells.
-static int solve_planned(ipc_engine* h, hipStream_t st, const CellPlan& pl)
-{
-    constexpr int NS = kPlanSlots;
-    const unsigned* counts = pl.counts; const unsigned* offsets = pl.offsets;
-    const size_t total = pl.total;
-    const int nb = h->plan.caps.n;
-    // cells whose chain is longer than the largest kernel variant of the policy go through the cluster
-    // solver below (one at a time, state in HBM: no length limit) instead of failing the matrix
-    const unsigned n_long = counts[nb] + counts[(kMaxBins + 1) + nb];
-    // solve: longest chains first
-    Se2View P = make_view(h);
-    Se3View P3 = make_view3(h);
-    const SolveParams sp{h->prm.fast_reject_iter_base, h->prm.slow_reject_iter_base};
-    // one slot's cells through the kernel variant of its bin
-    auto launch_slot = [&](int b, int nl, int n, const int2* cells, const CellOut& out, hipStream_t ls, unsigned* ctr) -> hipError_t {
+// One slot's cells through the kernel variant of its bin.  term_eps: the engine's, or 0 for g2o's literal loop (Se2View::term_eps).
+struct SlotLauncher {
+    const ipc_engine* h;
+    Se2View P; Se3View P3; SolveParams sp;
+    SlotLauncher(const ipc_engine* e, bool literal)
+        : h(e), P(make_view(e)), P3(make_view3(e)), sp{e->prm.fast_reject_iter_base, e->prm.slow_reject_iter_base}
+    {
+        if (literal) { P.term_eps = 0.0; P3.term_eps = 0.0; }
+    }
+    hipError_t operator()(int b, int nl, int n, const int2* cells, const CellOut& out, hipStream_t ls, unsigned* ctr) const
+    {
         int var = h->plan.variant[b];
         if (h->plan.latency_variant[b] >= 0 && n < h->plan.latency_below[b] * h->n_cu) var = h->plan.latency_variant[b];
         if (h->dim == 2)
@@ -1851,7 +1888,30 @@ static int solve_planned(ipc_engine* h, hipStream_t st, const CellPlan& pl)
                                              : launch_se2_block(nl, var, n, ls, P, cells, sp, out);
         if (var >= kLdsVariantBase3) return launch_se3_lds(nl, var - kLdsVariantBase3, n, ls, P3, cells, sp, out, ctr, h->n_cu);
         return launch_se3_block(nl, var, n, ls, P3, cells, sp, out);
-    };
+    }
+};
+
+static double borderline_band_of(const ipc_engine* h)
+{
+    return h->term_eps > 0 ? (h->borderline_band >= 0 ? h->borderline_band : 4.0 * std::sqrt(h->term_eps)) : 0.0;
+}
+
+// "Solve these planned lists" comes in two parts, so that the threshold sweep can run them apart (ipc_run_sweep): the first
+// pass -- the bin launches over the engine's streams (fork / join around `st`) and the cluster solver for chains beyond every
+// cell kernel -- and solve_collect: the collection of failed and borderline cells with its read-back, the literal re-solve
+// and the host-driven Levenberg retry.  solve_planned is one after the other: one code path for the batch step
+// (solve_rows_impl) and the online update (ipc_run_online); the results are left in d_chi / d_chitot / d_meta beside d_cells.
+static int solve_first_pass(ipc_engine* h, hipStream_t st, const CellPlan& pl)
+{
+    constexpr int NS = kPlanSlots;
+    const unsigned* counts = pl.counts; const unsigned* offsets = pl.offsets;
+    const size_t total = pl.total;
+    const int nb = h->plan.caps.n;
+    // cells whose chain is longer than the largest kernel variant of the policy go through the cluster
+    // solver below (one at a time, state in HBM: no length limit) instead of failing the matrix
+    const unsigned n_long = counts[nb] + counts[(kMaxBins + 1) + nb];
+    // solve: longest chains first
+    const SlotLauncher launch_slot(h, false);
     int launches = 0;
     HIPCHK(hipMemsetAsync(h->d_wave_ctr, 0, sizeof(unsigned) * NS, st));
     HIPCHK(hipEventRecord(h->ev0, st));
@@ -1900,7 +1960,37 @@ static int solve_planned(ipc_engine* h, hipStream_t st, const CellPlan& pl)
     h->last_cells = (int)total;
     h->last_long_cells = (int)n_long;
     h->last_lm_cells = h->last_literal_cells = 0;
-    const double band = h->term_eps > 0 ? (h->borderline_band >= 0 ? h->borderline_band : 4.0 * std::sqrt(h->term_eps)) : 0.0;
+    h->info_from_sweep = false;                          // (ipc_cell_info: the records of this solve)
+    return IPC_OK;
+}
+
+// The literal re-solve of the compact per-slot lists that a collection pass left in d_lit_cells (h_recount[s] cells at the
+// slot's own offset): the cell kernels with term_eps 0, results in d_lit_chi / d_lit_chitot / d_lit_meta at the same places.
+static int launch_literal_lists(ipc_engine* h, hipStream_t st, const unsigned* offsets)
+{
+    constexpr int NS = kPlanSlots;
+    const int nb = h->plan.caps.n;
+    const SlotLauncher launch_slot(h, true);                   // g2o's literal loop (Se2View::term_eps)
+    HIPCHK(hipMemsetAsync(h->d_wave_ctr, 0, sizeof(unsigned) * NS, st));
+    for (int b = nb - 1; b >= 0; --b) {
+        for (int nl = 2; nl >= 1; --nl) {
+            const int s = (nl == 1 ? 0 : (kMaxBins + 1)) + b;
+            const int n = h->h_recount[s];
+            if (!n) continue;
+            CellOut out{h->d_lit_chi + offsets[s], h->d_lit_chitot + offsets[s], h->d_lit_meta + offsets[s]};
+            const hipError_t e = launch_slot(b, nl, n, h->d_lit_cells + offsets[s], out, st, h->d_wave_ctr + s);
+            if (e != hipSuccess) return fail(IPC_ERR_HIP, "cell kernel launch failed: %s", hipGetErrorString(e));
+        }
+    }
+    return IPC_OK;
+}
+
+// `band`: the engine's (borderline_band_of); the sweep's first pass passes 0 -- only the failed cells are collected and retried.
+static int solve_collect(ipc_engine* h, hipStream_t st, const CellPlan& pl, double band)
+{
+    constexpr int NS = kPlanSlots;
+    const size_t total = pl.total;
+    const int nb = h->plan.caps.n;
     if (total && (h->lm_retry || band > 0.0)) {
         // The cells to solve again: failed linear solves (Levenberg retry by the host-driven solver: degenerate information,
         // rare) and borderline cells (the literal trial loop, by the cell kernels themselves over compact per-slot lists).
@@ -1919,18 +2009,7 @@ static int solve_planned(ipc_engine* h, hipStream_t st, const CellPlan& pl)
         int n_lit = 0;
         for (int s = 0; s < NS; ++s) n_lit += h->h_recount[s];
         if (n_lit) {
-            P.term_eps = 0.0; P3.term_eps = 0.0;                   // g2o's literal loop (Se2View::term_eps)
-            HIPCHK(hipMemsetAsync(h->d_wave_ctr, 0, sizeof(unsigned) * NS, st));
-            for (int b = nb - 1; b >= 0; --b) {
-                for (int nl = 2; nl >= 1; --nl) {
-                    const int s = (nl == 1 ? 0 : (kMaxBins + 1)) + b;
-                    const int n = h->h_recount[s];
-                    if (!n) continue;
-                    CellOut out{h->d_lit_chi + offsets[s], h->d_lit_chitot + offsets[s], h->d_lit_meta + offsets[s]};
-                    const hipError_t e = launch_slot(b, nl, n, h->d_lit_cells + offsets[s], out, st, h->d_wave_ctr + s);
-                    if (e != hipSuccess) return fail(IPC_ERR_HIP, "cell kernel launch failed: %s", hipGetErrorString(e));
-                }
-            }
+            if (int rc = launch_literal_lists(h, st, pl.offsets)) return rc;
             // (borderline cells beyond every cell kernel were solved by the cluster solver with the engine's term_eps; their
             // slot is not re-solved: counts of the long slots are skipped above because b < nb)
             hipLaunchKernelGGL(k_scatter_literal, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total,
@@ -1946,23 +2025,24 @@ static int solve_planned(ipc_engine* h, hipStream_t st, const CellPlan& pl)
     return IPC_OK;
 }
 
-// phase 0: all cells of the rank's rows.  Set-only mode (one rank): phase 1 = the diagonal cells, phase 2 = the pair cells
-// among the candidates whose diagonal bit is set in d_upper (left in place; the pair bits are OR-ed into it).
-static int solve_rows_impl(ipc_engine* h, int rank, int world, uint64_t* d_upper, void* stream, int phase)
+static int solve_planned(ipc_engine* h, hipStream_t st, const CellPlan& pl)
 {
-    HIPCHK(hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->own_stream;
-    const int N = h->N, words = (N + 63) / 64, rpr = ipc_rows_per_rank(N, world);
-    if (int rc = matrix_mode_enter(h, st)) return rc;
-    if (int rc = ensure_row_map(h, world)) return rc;
+    if (int rc = solve_first_pass(h, st, pl)) return rc;
+    return solve_collect(h, st, pl, borderline_band_of(h));
+}
+
+// The cell lists of the rank's rows into d_cells (ensure_row_map(world) has run).  `keep`: a plan made here is remembered
+// for the steps to come (the batch step; the sweep plans for itself alone and leaves that to the next ipc_run).
+static int plan_rows(ipc_engine* h, hipStream_t st, int rank, int world, int phase, const uint64_t* d_upper, bool keep,
+                     CellPlan& pl, bool& cached)
+{
+    const int N = h->N, words = (N + 63) / 64;
     const BinCaps bc = h->plan.caps;
     constexpr int NS = kPlanSlots;
-    if (phase != 2) HIPCHK(hipMemsetAsync(d_upper, 0, sizeof(uint64_t) * (size_t)rpr * words, st));
-    CellPlan pl;
     // The cell lists of this rank (d_cells, grouped by slot = (loop count, chain-length bin)) depend on the candidates,
     // the rank and the world only: a repeated step reuses them and skips the two planning passes with their read-back.
     // (The set-only phases plan from the diagonal bits of the step and are never cached.)
-    const bool cached = phase == 0 && h->plan_cached && h->plan_rank == rank && h->plan_world == world;
+    cached = phase == 0 && h->plan_cached && h->plan_rank == rank && h->plan_world == world;
     if (cached) {
         std::copy(h->plan_counts.begin(), h->plan_counts.end(), pl.counts);
         std::copy(h->plan_offsets.begin(), h->plan_offsets.end(), pl.offsets);
@@ -1975,13 +2055,30 @@ static int solve_rows_impl(ipc_engine* h, int rank, int world, uint64_t* d_upper
                 hipLaunchKernelGGL(k_plan, pgrid, pblock, 0, st, N, h->d_lo, h->d_hi, rows, nrows, bc, h->d_counters,
                                    h->d_offsets, cells, fill, phase, (const unsigned long long*)d_upper, words);
             })) return rc;
-        if (phase == 0) {
+        if (phase == 0 && keep) {
             h->plan_counts.assign(pl.counts, pl.counts + NS);
             h->plan_offsets.assign(pl.offsets, pl.offsets + NS);
             h->plan_total = pl.total; h->plan_rank = rank; h->plan_world = world;
             h->plan_cached = true;
         }
     }
+    return IPC_OK;
+}
+
+// phase 0: all cells of the rank's rows.  Set-only mode (one rank): phase 1 = the diagonal cells, phase 2 = the pair cells
+// among the candidates whose diagonal bit is set in d_upper (left in place; the pair bits are OR-ed into it).
+static int solve_rows_impl(ipc_engine* h, int rank, int world, uint64_t* d_upper, void* stream, int phase)
+{
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->own_stream;
+    const int N = h->N, words = (N + 63) / 64, rpr = ipc_rows_per_rank(N, world);
+    if (int rc = matrix_mode_enter(h, st)) return rc;
+    if (int rc = ensure_row_map(h, world)) return rc;
+    constexpr int NS = kPlanSlots;
+    if (phase != 2) HIPCHK(hipMemsetAsync(d_upper, 0, sizeof(uint64_t) * (size_t)rpr * words, st));
+    CellPlan pl;
+    bool cached = false;
+    if (int rc = plan_rows(h, st, rank, world, phase, d_upper, true, pl, cached)) return rc;
     const size_t total = pl.total;
     if (int rc = solve_planned(h, st, pl)) return rc;
     if (total)
@@ -2206,6 +2303,207 @@ extern "C" int ipc_run_online(ipc_engine_t* h, uint64_t* bits_out, uint8_t* acce
     return IPC_OK;
 }
 
+
+// ------------------------------------------------------------------------------------------
+// threshold sweep: the cells are solved once and decided at many (fast_reject_th, slow_reject_th) pairs
+// ------------------------------------------------------------------------------------------
+// The first pass of the sweep: every cell of the matrix through its bin's kernel (the launches of a batch step, world 1), the
+// Levenberg retry of the cells whose linear solve failed -- threshold independent, done once --, no borderline collection.
+// The records move into the sweep's own arrays; d_cells & co. are scratch of the call like for any other matrix call.
+static int sweep_first_pass(ipc_engine* h, hipStream_t st)
+{
+    constexpr int NS = kPlanSlots;
+    if (int rc = ensure_row_map(h, 1)) return rc;
+    CellPlan pl;
+    bool cached = false;
+    if (int rc = plan_rows(h, st, 0, 1, 0, nullptr, false, pl, cached)) return rc;
+    const size_t total = pl.total;
+    h->sw_valid = false;
+    if (total > h->sw_cap) {
+        const size_t cap = total + total / 8 + 1024;
+        h->sw_cap = 0;                                   // (until all six are there: a failure part way comes here again)
+        HIPCHK(h->d_sw_cells.alloc(cap));
+        HIPCHK(h->d_sw_chi.alloc(cap));
+        HIPCHK(h->d_sw_chitot.alloc(cap));
+        HIPCHK(h->d_sw_meta.alloc(cap));
+        HIPCHK(h->d_sw_lit.alloc(cap));
+        HIPCHK(h->d_sw_flags.alloc(cap));
+        h->sw_cap = cap;
+    }
+    if (!h->d_sw_slot_off) HIPCHK(h->d_sw_slot_off.alloc(NS + 1));
+    if (int rc = solve_first_pass(h, st, pl)) return rc;
+    if (total)
+        hipLaunchKernelGGL(k_sweep_init_flags, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total, (const int4*)h->d_meta,
+                           h->lm_retry, h->d_sw_flags);
+    HIPCHK(hipGetLastError());
+    if (int rc = solve_collect(h, st, pl, 0.0)) return rc;     // (band 0: the failed cells alone)
+    HIPCHK(hipMemcpyAsync(h->d_sw_cells, h->d_cells, sizeof(int2) * total, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(h->d_sw_chi, h->d_chi, sizeof(double) * total, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(h->d_sw_chitot, h->d_chitot, sizeof(double) * total, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(h->d_sw_meta, h->d_meta, sizeof(int4) * total, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemsetAsync(h->d_sw_lit, 0, sizeof(double) * total, st));
+    h->sw_counts.assign(pl.counts, pl.counts + NS);
+    h->sw_offsets.assign(pl.offsets, pl.offsets + NS);
+    unsigned slot_off[NS + 1];
+    for (int s = 0; s < NS; ++s) slot_off[s] = pl.offsets[s];
+    slot_off[NS] = (unsigned)total;
+    HIPCHK(hipMemcpyAsync(h->d_sw_slot_off, slot_off, sizeof slot_off, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));                    // (slot_off is a local; the records are complete when this returns)
+    h->sw_total = total;
+    h->sw_long = h->last_long_cells; h->sw_damped = h->last_lm_cells; h->sw_held = 0;
+    h->sw_valid = true;
+    return IPC_OK;
+}
+
+// The literal records that the pairs of this call ask for and the engine does not hold yet: collected on the device into the
+// compact per-slot lists, solved by the cell kernels with term_eps 0 (launch_literal_lists, ONE read-back of the counts); the
+// borderline cells of the long slots by the host-driven cluster solver with the convergence test off (resolve_failed_cells).
+static int sweep_literal(ipc_engine* h, hipStream_t st, int n_th, double band, int& n_new)
+{
+    constexpr int NS = kPlanSlots;
+    const size_t total = h->sw_total;
+    n_new = 0;
+    if (!total || !(band > 0.0)) return IPC_OK;
+    if (!h->d_failed || (int)total > h->failed_cap) {
+        h->failed_cap = std::max(16384, (int)(total + total / 8));
+        HIPCHK(h->d_failed.alloc((size_t)h->failed_cap + 1));
+    }
+    HIPCHK(hipMemsetAsync(h->d_recount, 0, sizeof(int) * (NS + 1), st));
+    hipLaunchKernelGGL(k_sweep_collect, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total, (const int*)h->d_sw_flags,
+                       (const double*)h->d_sw_chi, (const int2*)h->d_sw_cells, n_th, (const double*)h->d_sw_th, (const double*)h->d_sw_th + n_th,
+                       band, h->failed_cap, h->d_failed, h->d_recount, (const unsigned*)h->d_sw_slot_off, NS, h->d_lit_cells, h->d_lit_idx,
+                       h->plan.caps.n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h->h_recount, h->d_recount, sizeof(int) * (NS + 1), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    int n_lit = 0;
+    for (int s = 0; s < NS; ++s) n_lit += h->h_recount[s];
+    if (n_lit) {
+        if (int rc = launch_literal_lists(h, st, h->sw_offsets.data())) return rc;
+        hipLaunchKernelGGL(k_sweep_keep_literal, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total,
+                           (const unsigned*)h->d_sw_slot_off, NS, (const int*)h->d_recount, (const int*)h->d_lit_idx, (const double*)h->d_lit_chi,
+                           h->d_sw_lit, h->d_sw_flags);
+        HIPCHK(hipGetLastError());
+        n_new += n_lit; h->sw_held += n_lit;
+    }
+    const int n_host = std::min(h->h_recount[NS], h->failed_cap);
+    if (n_host) {
+        if (int rc = ensure_incremental(h, "ipc_run_sweep")) return rc;
+        HIPCHK(hipStreamSynchronize(st));
+        std::vector<int> idx(n_host);
+        HIPCHK(hipMemcpy(idx.data(), h->d_failed, sizeof(int) * n_host, hipMemcpyDeviceToHost));
+        std::sort(idx.begin(), idx.end());
+        for (int q = 0; q < n_host; ++q) {
+            int2 cell;
+            HIPCHK(hipMemcpy(&cell, h->d_sw_cells + idx[q], sizeof(int2), hipMemcpyDeviceToHost));
+            ClusterOut o;
+            if (int rc = host_cell_solve(h, cell, false, true, o)) return rc;      // g2o's literal trial loop, as resolve_failed_cells runs it
+            const int held = kSweepHeld;
+            HIPCHK(hipMemcpy(h->d_sw_lit + idx[q], &o.max_chi2, sizeof(double), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(h->d_sw_flags + idx[q], &held, sizeof(int), hipMemcpyHostToDevice));
+            ++h->sw_held; ++n_new;                       // (per cell: a failure part way leaves the count at what the flags say)
+        }
+        HIPCHK(hipStreamSynchronize(nullptr));                 // (NULL-stream copies are not ordered against the engine's non-blocking streams: copy_d2d_now)
+    }
+    return IPC_OK;
+}
+
+extern "C" int ipc_sweep_reset(ipc_engine_t* h)
+{
+    if (!h) return fail(IPC_ERR_ARG, "ipc_sweep_reset: NULL handle");
+    h->sw_valid = false;                                 // (the storage stays; the next ipc_run_sweep solves every cell)
+    if (h->info_from_sweep) { h->info_from_sweep = false; h->last_cells = 0; }
+    return IPC_OK;
+}
+
+extern "C" int ipc_run_sweep(ipc_engine_t* h, int n_th, const double* fast_th, const double* slow_th, uint64_t* bits_out,
+                             uint8_t* accepted_out, ipc_sweep_report_t* report)
+{
+    if (!h) return fail(IPC_ERR_ARG, "ipc_run_sweep: NULL handle");
+    if (n_th < 1) return fail(IPC_ERR_ARG, "ipc_run_sweep: %d thresholds (need >= 1)", n_th);
+    if (!fast_th || !slow_th) return fail(IPC_ERR_ARG, "ipc_run_sweep: fast_th or slow_th is NULL");
+    for (int t = 0; t < n_th; ++t)
+        if (fast_th[t] != fast_th[t] || slow_th[t] != slow_th[t]) return fail(IPC_ERR_ARG, "ipc_run_sweep: threshold pair %d is NaN", t);
+    if (h->N <= 0) return fail(IPC_ERR_STATE, "ipc_run_sweep: no candidates set");
+    HIPCHK(hipSetDevice(h->device));
+    const int N = h->N, words = (N + 63) / 64;
+    if (sizeof(unsigned long long) * (size_t)words > 60 * 1024) return fail(IPC_ERR_LIMIT, "ipc_run_sweep: N=%d exceeds the LDS-resident mask", N);
+    hipStream_t st = h->own_stream;
+    if (int rc = matrix_mode_enter(h, st)) return rc;
+    // Chunks: a threshold costs an upper triangle, a matrix, the accepted bytes and the live list.  The scratch grows only when a
+    // call needs more than it holds, up to a quarter of the free memory; nothing is allocated if not even one threshold fits.
+    const size_t mat = (size_t)N * words;
+    const int want = h->sweep_chunk > 0 ? std::min(n_th, h->sweep_chunk) : n_th;
+    int tc = (int)std::min<size_t>({(size_t)want, h->sw_mat_cap / mat, h->sw_vec_cap / (size_t)N});   // what the scratch holds
+    if (tc < want) {
+        size_t mem_free = 0, mem_total = 0;
+        HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
+        const size_t per = 2 * mat * sizeof(unsigned long long) + 5 * (size_t)N;
+        const size_t held = 2 * h->sw_mat_cap * sizeof(unsigned long long) + 5 * h->sw_vec_cap;     // (freed by the growth)
+        const size_t fit = ((mem_free + held) / 4) / per;
+        if (std::max<size_t>(fit, tc) < 1)
+            return fail(IPC_ERR_LIMIT, "ipc_run_sweep: one threshold of N=%d needs %zu MB of scratch, a quarter of the free memory is %zu MB",
+                        N, per >> 20, (mem_free / 4) >> 20);
+        const int grown = (int)std::min<size_t>((size_t)want, fit);
+        // (a scratch that holds some pairs is replaced only for the call's whole need or for twice what it holds: a budget that
+        // wavers by a pair from call to call must not free and allocate the four arrays every time)
+        if (grown > tc && (tc == 0 || grown == want || grown >= 2 * tc)) {
+            h->sw_mat_cap = h->sw_vec_cap = 0;           // (until all four are there: a failure part way comes here again)
+            h->d_sw_upper.reset(); h->d_sw_bits.reset(); h->d_sw_acc.reset(); h->d_sw_live.reset();
+            HIPCHK(h->d_sw_upper.alloc(mat * grown));
+            HIPCHK(h->d_sw_bits.alloc(mat * grown));
+            HIPCHK(h->d_sw_acc.alloc((size_t)N * grown));
+            HIPCHK(h->d_sw_live.alloc((size_t)N * grown));
+            h->sw_mat_cap = mat * grown; h->sw_vec_cap = (size_t)N * grown;
+            tc = grown;
+        }
+    }
+    if (n_th > h->sw_th_cap) {
+        h->sw_th_cap = 0;
+        HIPCHK(h->d_sw_th.alloc(2 * (size_t)n_th));
+        h->sw_th_cap = n_th;
+    }
+    HIPCHK(hipMemcpyAsync(h->d_sw_th, fast_th, sizeof(double) * n_th, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(h->d_sw_th + n_th, slow_th, sizeof(double) * n_th, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));                    // (pageable sources: the copies have left the caller's arrays when this returns)
+    ipc_sweep_report_t rep{};
+    rep.thresholds = n_th;
+    if (h->sw_valid) rep.reused_solve = 1;
+    else {
+        if (int rc = sweep_first_pass(h, st)) return rc;
+        rep.cells = (int)h->sw_total;
+    }
+    // the records ipc_cell_count / ipc_cell_info describe from here on: the held first pass
+    h->last_cells = (int)h->sw_total; h->last_long_cells = h->sw_long; h->last_lm_cells = h->sw_damped; h->last_literal_cells = 0;
+    h->info_from_sweep = true;
+    rep.long_cells = h->sw_long; rep.damped_cells = h->sw_damped;
+    const double band = borderline_band_of(h);
+    int n_new = 0;
+    if (int rc = sweep_literal(h, st, n_th, band, n_new)) return rc;
+    rep.literal_cells = n_new; rep.literal_held = h->sw_held;
+    const size_t total = h->sw_total;
+    const int tiles = ((N - 1) >> 6) + 1;
+    for (int t0 = 0; t0 < n_th; t0 += tc) {
+        const int n = std::min(tc, n_th - t0);
+        HIPCHK(hipMemsetAsync(h->d_sw_upper, 0, sizeof(unsigned long long) * mat * n, st));
+        if (total)
+            hipLaunchKernelGGL(k_sweep_scatter, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total, (const int2*)h->d_sw_cells,
+                               (const double*)h->d_sw_chi, (const double*)h->d_sw_lit, (const int*)h->d_sw_flags, n, (const double*)h->d_sw_th + t0,
+                               (const double*)h->d_sw_th + n_th + t0, band, words, mat, h->d_sw_upper);
+        hipLaunchKernelGGL(k_sweep_assemble, dim3(words, std::min((tiles + 3) / 4, 1024), n), dim3(256), 0, st, N, words, mat, (const int*)h->d_lo,
+                           (const int*)h->d_hi, (const unsigned long long*)h->d_sw_upper, h->d_sw_bits);
+        hipLaunchKernelGGL(k_sweep_set_max, dim3(n), dim3(1024), sizeof(unsigned long long) * words, st, N, words, mat, (const int*)h->d_order,
+                           (const unsigned long long*)h->d_sw_bits, h->d_sw_acc, h->d_sw_live);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+        if (bits_out) HIPCHK(hipMemcpy(bits_out + (size_t)t0 * mat, h->d_sw_bits, sizeof(uint64_t) * mat * n, hipMemcpyDeviceToHost));
+        if (accepted_out) HIPCHK(hipMemcpy(accepted_out + (size_t)t0 * N, h->d_sw_acc, (size_t)N * n, hipMemcpyDeviceToHost));
+        ++rep.chunks;
+    }
+    if (report) *report = rep;
+    return IPC_OK;
+}
+
 extern "C" int ipc_cell_count(ipc_engine_t* h, int* n_cells)
 {
     if (!h || !n_cells) return fail(IPC_ERR_ARG, "ipc_cell_count: NULL argument");
@@ -2223,10 +2521,11 @@ extern "C" int ipc_cell_info(ipc_engine_t* h, ipc_cell_info_t* out, int capacity
     std::vector<int2> cells(n);
     std::vector<double> chi(n), tot(n);
     std::vector<int4> meta(n);
-    HIPCHK(hipMemcpy(cells.data(), h->d_cells, sizeof(int2) * n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(chi.data(), h->d_chi, sizeof(double) * n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(tot.data(), h->d_chitot, sizeof(double) * n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(meta.data(), h->d_meta, sizeof(int4) * n, hipMemcpyDeviceToHost));
+    const bool sw = h->info_from_sweep;                  // after ipc_run_sweep: the first-pass records it holds
+    HIPCHK(hipMemcpy(cells.data(), sw ? h->d_sw_cells : h->d_cells, sizeof(int2) * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(chi.data(), sw ? h->d_sw_chi : h->d_chi, sizeof(double) * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(tot.data(), sw ? h->d_sw_chitot : h->d_chitot, sizeof(double) * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(meta.data(), sw ? h->d_sw_meta : h->d_meta, sizeof(int4) * n, hipMemcpyDeviceToHost));
     for (int c = 0; c < n; ++c) {
         ipc_cell_info_t& o = out[c];
         o.i = cells[c].x; o.j = cells[c].y;
@@ -2261,8 +2560,9 @@ extern "C" int ipc_solve_report(ipc_engine_t* h, ipc_solve_report_t* out)
     if (h->last_cells <= 0) return IPC_OK;
     unsigned host[3] = {0, 0, 0};
     HIPCHK(hipMemsetAsync(h->d_counters, 0, sizeof(unsigned) * 3, h->own_stream));
-    hipLaunchKernelGGL(k_report, dim3((h->last_cells + 255) / 256), dim3(256), 0, h->own_stream, h->last_cells, h->d_meta,
-                       h->d_chi, h->d_counters);
+    const bool sw = h->info_from_sweep;                  // after ipc_run_sweep: the first-pass records it holds
+    hipLaunchKernelGGL(k_report, dim3((h->last_cells + 255) / 256), dim3(256), 0, h->own_stream, h->last_cells,
+                       (const int4*)(sw ? h->d_sw_meta : h->d_meta), (const double*)(sw ? h->d_sw_chi : h->d_chi), h->d_counters);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(host, h->d_counters, sizeof host, hipMemcpyDeviceToHost, h->own_stream));
     HIPCHK(hipStreamSynchronize(h->own_stream));
