@@ -302,7 +302,45 @@ int ipc_run_sweep(ipc_engine_t* h, int n_th, const double* fast_th, const double
                   uint8_t* accepted_out, ipc_sweep_report_t* report);
 int ipc_sweep_reset(ipc_engine_t* h);      /* forget the held first pass */
 
-/* Diagnostics of the last ipc_solve_rows(), ipc_run_online() or ipc_run_sweep(): number of solved cells, and their records. */
+/* ---- Monte-Carlo batch ------------------------------------------------------------------------------
+ * The reference is run as Monte-Carlo experiments (bash/ipc_experiments_2D.sh: one dataset, ten outlier levels, ten draws each,
+ * ten ipc_tester_2D processes side by side): every draw shares the odometry chain and the first canonic_inliers loop closures,
+ * only the injected outliers differ (src/simulation.cpp:24-25, scripts/generateDataset.py).  ipc_run_batch stands in for n_runs
+ * such runs on one chain: the engine's candidate list (ipc_set_candidates / ipc_append_candidate) is the UNION U of all draws,
+ * N_u entries; run r is members[run_offsets[r] .. run_offsets[r+1]), indices into U, STRICTLY INCREASING, N_r >= 1 of them
+ * (run_offsets[0] = 0), and a candidate's local index in run r is its position in that list.  Every cell that some run needs --
+ * the diagonal cells of the members and the overlapping pairs that occur together in some run, no others -- is solved ONCE;
+ * each run then gets its own matrix and its own greedy set (the set of a sub-list is NOT the union's set restricted to it).
+ *
+ * Contract: run r's outputs equal, bit for bit, what ipc_run returns on an engine with the same chain, parameters and
+ * environment whose ipc_set_candidates was given the records of run r's members in that order.  With increasing members the
+ * processing order of the run's own list, (max id, local index), is the engine's order (ipc_candidate_order) restricted to the
+ * members.  As for ipc_run_sweep the claim rests on one fact: with the default policies a cell's kernel variant depends on its
+ * bin alone, so a cell's record does not depend on which list it was solved in.
+ * bits_out holds the runs back to back: run r is [N_r][ceil(N_r/64)] words in local indices, at word offset
+ * sum over q < r of N_q * ceil(N_q/64); accepted_out holds run r's N_r bytes at byte offset run_offsets[r].  bits_out,
+ * accepted_out and report may be NULL.
+ * The runs go through scatter / assemble / set-max device resident, in chunks of as many consecutive runs as fit a quarter of
+ * the free device memory (IPC_BATCH_CHUNK=<runs> and IPC_BATCH_BUDGET=<bytes>, read at ipc_create, cap a chunk).
+ * Errors: n_runs < 1, run_offsets or members NULL, an empty run, an index outside [0, N_u), members not strictly increasing:
+ * IPC_ERR_ARG; no candidates set: IPC_ERR_STATE; a run beyond the N limit of ipc_set_max, or a run that fits no chunk:
+ * IPC_ERR_LIMIT, before anything is allocated.  N_u itself is not bound by that limit: nothing runs a set-max over the union.
+ * The call enters matrix mode like every other matrix call and shares the cell buffers of ipc_solve_rows: afterwards
+ * ipc_cell_count, ipc_cell_info and ipc_solve_report describe the cells of THIS call, in union indices, and the next
+ * ipc_solve_rows / ipc_run plans its lists again.  The online matrix, the sweep's held first pass, the faithful state and the
+ * consensus set are neither read nor changed. */
+typedef struct {
+    int runs;                 /* R of this call                                                            */
+    int union_candidates;     /* N of the engine's list                                                    */
+    int cells;                /* cells solved: the distinct cells that some run needs                      */
+    long long cells_separate; /* sum over the runs of the cells a separate ipc_run on that list would solve */
+    int long_cells, damped_cells, literal_cells;   /* as in ipc_solve_report_t, over the solved cells       */
+    int chunks;               /* groups of runs that went through scatter / assemble / set-max together    */
+} ipc_batch_report_t;
+int ipc_run_batch(ipc_engine_t* h, int n_runs, const int* run_offsets, const int* members, uint64_t* bits_out,
+                  uint8_t* accepted_out, ipc_batch_report_t* report);
+
+/* Diagnostics of the last ipc_solve_rows(), ipc_run_online(), ipc_run_sweep() or ipc_run_batch(): number of solved cells, and their records. */
 int ipc_cell_count(ipc_engine_t* h, int* n_cells);
 int ipc_cell_info(ipc_engine_t* h, ipc_cell_info_t* out, int capacity);
 

@@ -36,6 +36,7 @@ SYMBOLS = [
     "ipc_append_odometry", "ipc_reserve_vertices", "ipc_vertex_count",
     "ipc_run_online", "ipc_online_covered", "ipc_online_reset", "ipc_reserve_candidates", "ipc_debug_live_resources",
     "ipc_run_sweep", "ipc_sweep_reset",
+    "ipc_run_batch",
 ]
 
 
@@ -75,6 +76,11 @@ class OnlineReport(C.Structure):
 class SweepReport(C.Structure):
     _fields_ = [("thresholds", C.c_int), ("cells", C.c_int), ("long_cells", C.c_int), ("damped_cells", C.c_int),
                 ("literal_cells", C.c_int), ("literal_held", C.c_int), ("reused_solve", C.c_int), ("chunks", C.c_int)]
+
+
+class BatchReport(C.Structure):
+    _fields_ = [("runs", C.c_int), ("union_candidates", C.c_int), ("cells", C.c_int), ("cells_separate", C.c_longlong),
+                ("long_cells", C.c_int), ("damped_cells", C.c_int), ("literal_cells", C.c_int), ("chunks", C.c_int)]
 
 
 CELL_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("lo", "<i4"), ("hi", "<i4"), ("max_chi2", "<f8"),
@@ -127,6 +133,7 @@ def load():
     lib.ipc_reserve_candidates.argtypes = [vp, ip]
     lib.ipc_run_sweep.argtypes = [vp, ip, vp, vp, vp, vp, C.POINTER(SweepReport)]
     lib.ipc_sweep_reset.argtypes = [vp]
+    lib.ipc_run_batch.argtypes = [vp, ip, vp, vp, vp, vp, C.POINTER(BatchReport)]
     lib.ipc_run_sharded.argtypes = [C.POINTER(vp), ip, vp, vp]
     lib.ipc_run_set_only.argtypes = [vp, vp, C.POINTER(ip)]
     lib.ipc_cell_count.argtypes = [vp, C.POINTER(ip)]

@@ -176,6 +176,30 @@ class IPC:
         """Forget the sweep's held first pass (ipc_sweep_reset): the next run_sweep solves every cell."""
         capi.check(self.lib.ipc_sweep_reset(self.h))
 
+    # ---- Monte-Carlo batch: the cells solved once, assembled into many candidate lists ----
+    def run_batch(self, runs, want_bits=False):
+        """ipc_run_batch: `runs` is a list of int arrays, each a strictly increasing selection of this engine's candidates (the
+        union list); entry r is what run() returns on a fresh engine given those candidates in that order.  Returns (list of
+        accepted [N_r] uint8, report dict), or (list of bits [N_r, words_r] uint64, list of accepted, report) with want_bits.
+        A batch has no single set: getMaxConsensusSet() is left as it was."""
+        runs = [np.ascontiguousarray(r, dtype=np.int32).reshape(-1) for r in runs]
+        sizes = [int(r.shape[0]) for r in runs]
+        offsets = np.zeros(len(runs) + 1, dtype=np.int32)
+        offsets[1:] = np.cumsum(sizes)
+        members = np.ascontiguousarray(np.concatenate(runs) if runs else np.zeros(0), dtype=np.int32)
+        mats = [n * ((n + 63) // 64) for n in sizes]
+        acc = np.zeros(max(int(offsets[-1]), 1), dtype=np.uint8)
+        bits = np.zeros(max(sum(mats), 1), dtype=np.uint64) if want_bits else None
+        r = capi.BatchReport()
+        capi.check(self.lib.ipc_run_batch(self.h, len(runs), _p(offsets), _p(members), _p(bits) if want_bits else None, _p(acc),
+                                          C.byref(r)))
+        report = {k: getattr(r, k) for k, _ in capi.BatchReport._fields_}
+        accs = [acc[offsets[q]:offsets[q + 1]] for q in range(len(runs))]
+        if not want_bits:
+            return accs, report
+        mo = np.concatenate([[0], np.cumsum(mats)])
+        return [bits[mo[q]:mo[q + 1]].reshape(sizes[q], -1) for q in range(len(runs))], accs, report
+
     def consistency_matrix(self):
         bits, _ = self.run()
         return unpack_bits(bits, self.N)

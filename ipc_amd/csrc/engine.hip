@@ -708,6 +708,7 @@ static hipError_t launch_se3_lds(int nl, int idx, int n, hipStream_t st, const S
 #undef IPC_LCASE
 }
 
+struct BatchRun;                                       // (batch_kernels.hpp)
 struct ipc_engine {
     // The engine's one stream of its own.  FIRST member, so that it dies LAST: the solvers below wait for their last launch
     // on it when they die, and every buffer and event goes before the stream does.
@@ -794,6 +795,18 @@ struct ipc_engine {
     DevBuf<unsigned long long> d_sw_upper, d_sw_bits; DevBuf<unsigned char> d_sw_acc; DevBuf<int> d_sw_live;
     size_t sw_mat_cap = 0, sw_vec_cap = 0;             // capacity in words per matrix array / in entries per vector array
     int sweep_chunk = 0;                               // IPC_SWEEP_CHUNK: cap on the thresholds per chunk (0: none)
+    // Monte-Carlo batch (ipc_run_batch): the cells are planned into d_cells & co. like those of any matrix call;
+    // what the call holds of its own is the membership words [N][mw] with the 64-bit counter of cells_separate, and the scratch
+    // of a chunk of runs: upper triangles and matrices (words), accepted bytes, five int vectors per run (live, lo, hi, order,
+    // members), the local-index maps [runs][N] and the descriptors.  One pinned buffer stages every upload.
+    DevBuf<unsigned long long> d_bt_memb, d_bt_sep; size_t bt_memb_cap = 0;
+    DevBuf<unsigned long long> d_bt_upper, d_bt_bits; size_t bt_mat_cap = 0;
+    DevBuf<unsigned char> d_bt_acc; DevBuf<int> d_bt_vec; size_t bt_vec_cap = 0;
+    DevBuf<int> d_bt_loc; size_t bt_loc_cap = 0;
+    DevBuf<BatchRun> d_bt_runs; size_t bt_runs_cap = 0;
+    PinnedBuf<unsigned long long> h_bt_stage; size_t bt_stage_cap = 0;   // in 8-byte words
+    int batch_chunk = 0;                               // IPC_BATCH_CHUNK: cap on the runs per chunk (0: none)
+    size_t batch_budget = 0;                           // IPC_BATCH_BUDGET: cap in bytes on a chunk's scratch (0: a quarter of the free memory alone)
     // incremental mode / final map (SE2)
     std::vector<double> h_odom_meas, h_odom_info;      // file values, for the un-scaled chain
     std::vector<int> h_from, h_to, cns;
@@ -1097,6 +1110,8 @@ extern "C" int ipc_create(int dim, int n_vertices, const double* odom_meas, cons
         }
     }
     if (const char* sc = getenv("IPC_SWEEP_CHUNK")) { if (*sc) h->sweep_chunk = std::max(0, atoi(sc)); }
+    if (const char* bc = getenv("IPC_BATCH_CHUNK")) { if (*bc) h->batch_chunk = std::max(0, atoi(bc)); }
+    if (const char* bb = getenv("IPC_BATCH_BUDGET")) { if (*bb) h->batch_budget = (size_t)std::max(0ll, atoll(bb)); }
     if (const char* sf = getenv("IPC_SLOW_FIRST")) { if (*sf) h->slow_first_iterations = std::max(0, atoi(sf)); }
     if (const char* rb = getenv("IPC_ROW_BALANCE")) {
         if (!strcmp(rb, "cyclic")) h->row_policy = 0;
@@ -1641,6 +1656,7 @@ __device__ __forceinline__ int slot_of_cell(const unsigned* slot_off, int nslots
     return lo;
 }
 #include "sweep_kernels.hpp"
+#include "batch_kernels.hpp"
 // Failed cells -> list (host-driven Levenberg retry, rare); borderline cells -> the compact list of their slot (lit_cells /
 // lit_idx at the slot's own offset: a slot has room for all of its cells), counted per slot in recount[0 .. nslots).
 __global__ void k_collect_failed(int ncells, const int4* meta, const double* chi, const int2* cells, double fast_th,
@@ -2498,6 +2514,192 @@ extern "C" int ipc_run_sweep(ipc_engine_t* h, int n_th, const double* fast_th, c
         HIPCHK(hipStreamSynchronize(st));
         if (bits_out) HIPCHK(hipMemcpy(bits_out + (size_t)t0 * mat, h->d_sw_bits, sizeof(uint64_t) * mat * n, hipMemcpyDeviceToHost));
         if (accepted_out) HIPCHK(hipMemcpy(accepted_out + (size_t)t0 * N, h->d_sw_acc, (size_t)N * n, hipMemcpyDeviceToHost));
+        ++rep.chunks;
+    }
+    if (report) *report = rep;
+    return IPC_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Monte-Carlo batch: the cells solved once, assembled into many candidate lists
+// ------------------------------------------------------------------------------------------
+extern "C" int ipc_run_batch(ipc_engine_t* h, int n_runs, const int* run_offsets, const int* members, uint64_t* bits_out,
+                             uint8_t* accepted_out, ipc_batch_report_t* report)
+{
+    if (!h) return fail(IPC_ERR_ARG, "ipc_run_batch: NULL handle");
+    if (n_runs < 1) return fail(IPC_ERR_ARG, "ipc_run_batch: %d runs (need >= 1)", n_runs);
+    if (!run_offsets || !members) return fail(IPC_ERR_ARG, "ipc_run_batch: run_offsets or members is NULL");
+    if (h->N <= 0) return fail(IPC_ERR_STATE, "ipc_run_batch: no candidates set");
+    const int N = h->N, R = n_runs, mw = (R + 63) / 64;
+    for (int r = 0; r < R; ++r) {
+        const int a = run_offsets[r], b = run_offsets[r + 1];
+        if (a < 0 || b <= a) return fail(IPC_ERR_ARG, "ipc_run_batch: run %d is empty (offsets %d .. %d)", r, a, b);
+        for (int k = a; k < b; ++k) {
+            if (members[k] < 0 || members[k] >= N) return fail(IPC_ERR_ARG, "ipc_run_batch: run %d names candidate %d outside 0..%d", r, members[k], N - 1);
+            if (k > a && members[k] <= members[k - 1]) return fail(IPC_ERR_ARG, "ipc_run_batch: the members of run %d are not strictly increasing", r);
+        }
+    }
+    if (run_offsets[0] != 0) return fail(IPC_ERR_ARG, "ipc_run_batch: run_offsets[0] = %d (need 0)", run_offsets[0]);
+    // A run costs an upper triangle and a matrix, the accepted bytes, five int vectors, its local-index map and its descriptor.
+    auto run_n = [&](int r) { return run_offsets[r + 1] - run_offsets[r]; };
+    auto run_bytes = [&](int r) {
+        const size_t n = (size_t)run_n(r), words = (n + 63) / 64;
+        return 2 * n * words * sizeof(unsigned long long) + n * (1 + 5 * sizeof(int)) + (size_t)N * sizeof(int) + sizeof(BatchRun);
+    };
+    for (int r = 0; r < R; ++r)
+        if (sizeof(unsigned long long) * (size_t)((run_n(r) + 63) / 64) > 60 * 1024)
+            return fail(IPC_ERR_LIMIT, "ipc_run_batch: run %d with %d candidates exceeds the LDS-resident mask", r, run_n(r));
+    HIPCHK(hipSetDevice(h->device));
+    // Chunks of consecutive runs: as many as fit a quarter of the free memory (the scratch the engine holds counts as free: a
+    // growth replaces it), capped by IPC_BATCH_CHUNK runs and IPC_BATCH_BUDGET bytes.  Nothing is allocated if a run fits none.
+    size_t budget = 0;
+    {
+        size_t mem_free = 0, mem_total = 0;
+        HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
+        const size_t held = 2 * h->bt_mat_cap * sizeof(unsigned long long) + h->bt_vec_cap * (1 + 5 * sizeof(int)) + h->bt_loc_cap * sizeof(int);
+        budget = (mem_free + held) / 4;
+        if (h->batch_budget) budget = std::min(budget, h->batch_budget);
+    }
+    std::vector<int> chunk_first{0};                     // first run of every chunk, then R
+    {
+        size_t used = 0;
+        for (int r = 0; r < R; ++r) {
+            const size_t need = run_bytes(r);
+            if (need > budget)
+                return fail(IPC_ERR_LIMIT, "ipc_run_batch: run %d with %d candidates needs %zu KB of scratch, the budget of a chunk is %zu KB",
+                            r, run_n(r), need >> 10, budget >> 10);
+            const int in_chunk = r - chunk_first.back();
+            if (in_chunk > 0 && (used + need > budget || (h->batch_chunk > 0 && in_chunk >= h->batch_chunk))) { chunk_first.push_back(r); used = 0; }
+            used += need;
+        }
+        chunk_first.push_back(R);
+    }
+    const int n_chunks = (int)chunk_first.size() - 1;
+    size_t need_mat = 0, need_vec = 0, need_runs = 0;    // the largest chunk, per array
+    for (int q = 0; q < n_chunks; ++q) {
+        size_t mat = 0;
+        for (int r = chunk_first[q]; r < chunk_first[q + 1]; ++r) mat += (size_t)run_n(r) * ((run_n(r) + 63) / 64);
+        need_mat = std::max(need_mat, mat);
+        need_vec = std::max(need_vec, (size_t)(run_offsets[chunk_first[q + 1]] - run_offsets[chunk_first[q]]));
+        need_runs = std::max(need_runs, (size_t)(chunk_first[q + 1] - chunk_first[q]));
+    }
+    const size_t need_loc = need_runs * (size_t)N, need_memb = (size_t)N * mw;
+    hipStream_t st = h->own_stream;
+    if (int rc = matrix_mode_enter(h, st)) return rc;
+    if (need_mat > h->bt_mat_cap) {
+        h->bt_mat_cap = 0;                               // (until both are there: a failure part way comes here again)
+        h->d_bt_upper.reset(); h->d_bt_bits.reset();
+        HIPCHK(h->d_bt_upper.alloc(need_mat));
+        HIPCHK(h->d_bt_bits.alloc(need_mat));
+        h->bt_mat_cap = need_mat;
+    }
+    if (need_vec > h->bt_vec_cap) {
+        h->bt_vec_cap = 0;
+        h->d_bt_acc.reset(); h->d_bt_vec.reset();
+        HIPCHK(h->d_bt_acc.alloc(need_vec));
+        HIPCHK(h->d_bt_vec.alloc(5 * need_vec));
+        h->bt_vec_cap = need_vec;
+    }
+    if (need_loc > h->bt_loc_cap) {
+        h->bt_loc_cap = 0;
+        HIPCHK(h->d_bt_loc.alloc(need_loc));
+        h->bt_loc_cap = need_loc;
+    }
+    if (need_runs > h->bt_runs_cap) {
+        h->bt_runs_cap = 0;
+        HIPCHK(h->d_bt_runs.alloc(need_runs));
+        h->bt_runs_cap = need_runs;
+    }
+    if (need_memb > h->bt_memb_cap) {
+        h->bt_memb_cap = 0;
+        HIPCHK(h->d_bt_memb.alloc(need_memb));
+        if (!h->d_bt_sep) HIPCHK(h->d_bt_sep.alloc(1));
+        h->bt_memb_cap = need_memb;
+    }
+    // the pinned staging, in 8-byte words: the membership words, later a chunk's descriptors, orders, members and maps
+    const size_t stage_runs = (need_runs * sizeof(BatchRun) + 7) / 8, stage_vec = (need_vec * sizeof(int) + 7) / 8;
+    const size_t need_stage = std::max(need_memb, stage_runs + 2 * stage_vec + (need_loc * sizeof(int) + 7) / 8);
+    if (need_stage > h->bt_stage_cap) {
+        h->bt_stage_cap = 0;
+        HIPCHK(h->h_bt_stage.alloc(need_stage));
+        h->bt_stage_cap = need_stage;
+    }
+    // membership words
+    unsigned long long* memb = h->h_bt_stage;
+    std::fill(memb, memb + need_memb, 0ull);
+    for (int r = 0; r < R; ++r)
+        for (int k = run_offsets[r]; k < run_offsets[r + 1]; ++k) memb[(size_t)members[k] * mw + (r >> 6)] |= 1ull << (r & 63);
+    HIPCHK(hipMemcpyAsync(h->d_bt_memb, memb, sizeof(unsigned long long) * need_memb, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(h->d_bt_sep, 0, sizeof(unsigned long long), st));
+    // The cells some run needs, into d_cells & co. (the cached plan of the batch path is gone: plan_cells), in the row order of
+    // a one-rank step; then the engine's own solve -- borderline literal re-solves and Levenberg retries once per shared cell.
+    if (int rc = ensure_row_map(h, 1)) return rc;
+    CellPlan pl;
+    {
+        const BinCaps bc = h->plan.caps;
+        const dim3 pgrid((N + 255) / 256, std::max(1, std::min(N, 2048))), pblock(256);
+        if (int rc = plan_cells(h, st, pl, 0, [&](int2* cells, int fill) {
+                hipLaunchKernelGGL(k_plan_batch, pgrid, pblock, 0, st, N, (const int*)h->d_lo, (const int*)h->d_hi, (const int*)h->d_rowperm, N, bc,
+                                   h->d_counters, (const unsigned*)h->d_offsets, cells, fill, (const unsigned long long*)h->d_bt_memb, mw, h->d_bt_sep);
+            })) return rc;
+    }
+    const size_t total = pl.total;
+    if (int rc = solve_planned(h, st, pl)) return rc;
+    ipc_batch_report_t rep{};
+    rep.runs = R; rep.union_candidates = N; rep.cells = (int)total;
+    rep.long_cells = h->last_long_cells; rep.damped_cells = h->last_lm_cells; rep.literal_cells = h->last_literal_cells;
+    {
+        unsigned long long sep = 0;
+        HIPCHK(hipMemcpyAsync(&sep, h->d_bt_sep, sizeof sep, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));                // (also: the membership words have left the staging buffer)
+        rep.cells_separate = (long long)sep;
+    }
+    std::vector<int> locmap((size_t)N);
+    size_t bits_done = 0;                                // words of bits_out written so far
+    for (int q = 0; q < n_chunks; ++q) {
+        const int c0 = chunk_first[q], n = chunk_first[q + 1] - c0, v0 = run_offsets[c0];
+        const size_t nvec = (size_t)(run_offsets[c0 + n] - v0);
+        BatchRun* s_runs = (BatchRun*)(unsigned long long*)h->h_bt_stage;
+        int* s_order = (int*)((unsigned long long*)h->h_bt_stage + stage_runs);
+        int* s_memb = (int*)((unsigned long long*)h->h_bt_stage + stage_runs + stage_vec);
+        int* s_loc = (int*)((unsigned long long*)h->h_bt_stage + stage_runs + 2 * stage_vec);
+        size_t mat = 0;
+        int max_n = 0;
+        for (int rc = 0; rc < n; ++rc) {
+            const int r = c0 + rc, nr = run_n(r), words = (nr + 63) / 64, voff = run_offsets[r] - v0;
+            s_runs[rc] = BatchRun{nr, words, voff, 0, (long long)mat};
+            mat += (size_t)nr * words;
+            max_n = std::max(max_n, nr);
+            int* loc = s_loc + (size_t)rc * N;
+            std::fill(loc, loc + N, -1);
+            for (int k = 0; k < nr; ++k) { loc[members[run_offsets[r] + k]] = k; s_memb[voff + k] = members[run_offsets[r] + k]; }
+            // the run's own processing order: the engine's (max id, index), restricted to the members and relabelled
+            int pos = 0;
+            for (int p = 0; p < N; ++p) { const int l = loc[h->order[p]]; if (l >= 0) s_order[voff + pos++] = l; }
+        }
+        int* d_live = h->d_bt_vec; int* d_lo_r = d_live + h->bt_vec_cap; int* d_hi_r = d_lo_r + h->bt_vec_cap;
+        int* d_order_r = d_hi_r + h->bt_vec_cap; int* d_memb_r = d_order_r + h->bt_vec_cap;
+        HIPCHK(hipMemcpyAsync(h->d_bt_runs, s_runs, sizeof(BatchRun) * n, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_order_r, s_order, sizeof(int) * nvec, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_memb_r, s_memb, sizeof(int) * nvec, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(h->d_bt_loc, s_loc, sizeof(int) * (size_t)n * N, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(h->d_bt_upper, 0, sizeof(unsigned long long) * mat, st));
+        const int max_words = (max_n + 63) / 64, max_tiles = ((max_n - 1) >> 6) + 1;
+        hipLaunchKernelGGL(k_batch_gather, dim3((max_n + 255) / 256, n), dim3(256), 0, st, (const BatchRun*)h->d_bt_runs, (const int*)d_memb_r,
+                           (const int*)h->d_lo, (const int*)h->d_hi, d_lo_r, d_hi_r);
+        if (total)
+            hipLaunchKernelGGL(k_batch_scatter, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total, (const int2*)h->d_cells,
+                               (const double*)h->d_chi, h->prm.fast_reject_th, h->prm.slow_reject_th, (const unsigned long long*)h->d_bt_memb, mw, c0, n,
+                               N, (const BatchRun*)h->d_bt_runs, (const int*)h->d_bt_loc, h->d_bt_upper);
+        hipLaunchKernelGGL(k_batch_assemble, dim3(max_words, std::min((max_tiles + 3) / 4, 1024), n), dim3(256), 0, st, (const BatchRun*)h->d_bt_runs,
+                           (const int*)d_lo_r, (const int*)d_hi_r, (const unsigned long long*)h->d_bt_upper, h->d_bt_bits);
+        hipLaunchKernelGGL(k_batch_set_max, dim3(n), dim3(1024), sizeof(unsigned long long) * max_words, st, (const BatchRun*)h->d_bt_runs,
+                           (const int*)d_order_r, (const unsigned long long*)h->d_bt_bits, h->d_bt_acc, d_live);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));                // (the staging buffer is free for the next chunk when this returns)
+        if (bits_out) HIPCHK(hipMemcpy(bits_out + bits_done, h->d_bt_bits, sizeof(uint64_t) * mat, hipMemcpyDeviceToHost));
+        if (accepted_out) HIPCHK(hipMemcpy(accepted_out + v0, h->d_bt_acc, nvec, hipMemcpyDeviceToHost));
+        bits_done += mat;
         ++rep.chunks;
     }
     if (report) *report = rep;
