@@ -35,7 +35,6 @@ struct WaveScratch {          // per cell (one wave, or a pair of waves), LDS
     LoopState ls[2][NL];
     double lvec[NL][2][3];
     double red[4][32];        // wide reduction, one row per wave of the cell
-    double gam[4][NL * 9];    // Gamma_l of the capacitance assembly (each wave keeps its own copy)
 };
 
 // Mailbox of a wave pair that solves one cell together (W == 2).  The two waves run on different
@@ -134,6 +133,19 @@ __device__ __forceinline__ bool ldl_solve(double (&A)[N][N], double (&b)[N])
         b[i] = v;
     }
     return ok;
+}
+
+// Gamma_l[i][a] of the capacitance assembly, from A = c_f cz - s_f sz, B = s_f cz + c_f sz (from-pose times measurement
+// rotation), K = (-(y_t - y_g), x_t - x_g) and the loop's direction sigma.  Everything is formed first and then selected,
+// so that i and a, which differ from lane to lane, cost selects and no branches.
+__device__ __forceinline__ double se2_gamma(double Aq, double Bq, double Kx, double Ky, double sigma, int i, int a)
+{
+    const double g02 = Aq * Kx + Bq * Ky, g12 = -Bq * Kx + Aq * Ky, nB = -Bq;   // formed first: selects, not branches
+    const double g0 = a == 0 ? Aq : (a == 1 ? Bq : g02);
+    const double g1 = a == 0 ? nB : (a == 1 ? Aq : g12);
+    const double g2 = a == 2 ? 1.0 : 0.0;
+    const double g = i == 0 ? g0 : (i == 1 ? g1 : g2);
+    return sigma * g;
 }
 
 template <int V> struct IntC { static constexpr int value = V; };
@@ -450,17 +462,6 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
         const double cP = st.pf[3] * q.cz - st.pf[4] * q.sz, sP = st.pf[4] * q.cz + st.pf[3] * q.sz;
         st.g[0] = cP * q0 - sP * q1; st.g[1] = sP * q0 + cP * q1; st.g[2] = q2;
     };
-    auto loop_quad = [&](int l) -> double {
-        const LoopConst& q = sh.lc[l];
-        const LoopState& st = sh.ls[cur][l];
-        Pose2 a{st.pf[0], st.pf[1], st.pf[2], st.pf[3], st.pf[4]};
-        Pose2 b{st.pt[0], st.pt[1], st.pt[2], st.pt[3], st.pt[4]};
-        double wx, wy, wth;
-        se2_apply_J(a, b, q.cz, q.sz, sh.lvec[l][0][0], sh.lvec[l][0][1], sh.lvec[l][0][2], sh.lvec[l][1][0],
-                    sh.lvec[l][1][1], sh.lvec[l][1][2], wx, wy, wth);
-        Sym3 om{q.om[0], q.om[1], q.om[2], q.om[3], q.om[4], q.om[5]};
-        return om.quad(wx, wy, wth);
-    };
 
     // One sweep over the chain.
     //   MODE 0: errors of the committed poses X            -> e, chi2, loop state buffer `bsel`
@@ -744,86 +745,158 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
             IPC_WTICK(tmB1)
             // ---- capacitance solve, lane-parallel (a uniform 6x6 solve in registers would pin ~150
             // VGPRs while the whole chain state is live):
-            //   lane l*9+i*3+a   : Gamma_l[i][a]                              -> gam[.]
             //   lane r*(NS+1)+c  : S[r][c] (c < NS) / rhs d[r] (c == NS), then Gauss-Jordan in place
-            auto wtv = [&](int k) -> double {
-                double t = sh.red[0][k];
-#pragma unroll
-                for (int o = 1; o < W; ++o) t += sh.red[o][k];
-                return t;
-            };
-            double* gamw = sh.gam[wsub];
-            if (lane < NL * 9) {
-                const int l = lane / 9, i = (lane % 9) / 3, a = lane % 3;
-                const LoopConst& q = sh.lc[l];
-                const LoopState& st = sh.ls[cur][l];
-                const double Aq = st.pf[3] * q.cz - st.pf[4] * q.sz, Bq = st.pf[4] * q.cz + st.pf[3] * q.sz;
-                const double Kx = -(st.pt[1] - gauge.y), Ky = st.pt[0] - gauge.x;
-                double g;
-                if (i == 0) g = a == 0 ? Aq : (a == 1 ? Bq : Aq * Kx + Bq * Ky);
-                else if (i == 1) g = a == 0 ? -Bq : (a == 1 ? Aq : -Bq * Kx + Aq * Ky);
-                else g = a == 2 ? 1.0 : 0.0;
-                gamw[lane] = q.sigma * g;
-            }
-            wave_sync();
+            // With one wave per SIMD nothing hides an LDS round trip, so the block makes as few as it can:
+            //   * every LDS operand (loop constants and state, the partial sums, the end-point vectors) is fetched
+            //     once, as one batch, with indices clamped instead of predicated so that no branch splits the batch;
+            //   * lane l*9+i*3+a forms Gamma_l[i][a] (se2_gamma) and the lanes of S fetch the six entries they use
+            //     with cross-lane reads issued together: one round trip instead of a store to LDS, a wave_sync and
+            //     serialised re-reads;
+            //   * what does not depend on the solve sits under those reads (the sums over the cell's waves, the loops'
+            //     part of b^T H b) and under the pivots' cross-lane reads and reciprocals (alpha, |h_sd|);
+            //   * nu's cross-lane reads (three of mu, three of Gamma's column) are issued together.
             constexpr int RS = NS + 1;                    // row stride of the augmented system
-            double val = 0.0;
-            const int r = lane / RS, c = lane % RS;
-            if (lane < NS * RS) {
-                const int l1 = r / 3, i = r % 3;
-                const double g10 = gamw[l1 * 9 + i * 3], g11 = gamw[l1 * 9 + i * 3 + 1], g12 = gamw[l1 * 9 + i * 3 + 2];
-                if (c < NS) {
-                    const int l2 = c / 3, k = c % 3;
-                    const int mb = l1 == l2 ? (l1 == 0 ? 5 : 19) : 25;
-                    const double m00 = wtv(mb), m01 = wtv(mb + 1), m02 = wtv(mb + 2), m11 = wtv(mb + 3), m12 = wtv(mb + 4), m22 = wtv(mb + 5);
-                    const double t0 = g10 * m00 + g11 * m01 + g12 * m02;
-                    const double t1 = g10 * m01 + g11 * m11 + g12 * m12;
-                    const double t2 = g10 * m02 + g11 * m12 + g12 * m22;
-                    val = t0 * gamw[l2 * 9 + k * 3] + t1 * gamw[l2 * 9 + k * 3 + 1] + t2 * gamw[l2 * 9 + k * 3 + 2];
-                    if (l1 == l2) {
-                        const int lo_ = i < k ? i : k, hi_ = i < k ? k : i;
-                        val += sh.lc[l1].sg[lo_ * 3 - lo_ * (lo_ - 1) / 2 + (hi_ - lo_)];
-                    }
-                } else {
-                    const int wb = l1 == 0 ? 2 : 16;
-                    val = sh.ls[cur][l1].e[i] - (g10 * wtv(wb) + g11 * wtv(wb + 1) + g12 * wtv(wb + 2));
+            // The lane's place in the system is recomputed here in every iteration: derived from `lane` itself, the
+            // indices and the dozen lane masks are hoisted out of the dog-leg loop and live (spilled) across all of it.
+            int bl = lane;
+            asm volatile("" : "+v"(bl));
+            const int r = bl / RS, c = bl % RS;
+            const bool inS = bl < NS * RS;
+            const int l1 = (NL > 1 && inS) ? r / 3 : 0, i = r % 3;     // loop / component of the row
+            const int l2 = (NL > 1 && c < NS) ? c / 3 : 0, k3 = c % 3; // ... of the column (k3 also: nu's column)
+            const int lq_l = bl < NL ? bl : 0;
+            // -- the batch --
+            // Gamma: lane l*9+i*3+a forms Gamma_l[i][a] (the lanes beyond form loop 0's again; nobody reads them)
+            const int g_l = (NL > 1 && bl < NL * 9) ? bl / 9 : 0, g_i = (bl % 9) / 3, g_a = bl % 3;
+            const LoopConst& qg = sh.lc[g_l];
+            const LoopState& sg_ = sh.ls[cur][g_l];
+            const double gcz = qg.cz, gsz = qg.sz, gsig = qg.sigma;
+            const double gpc = sg_.pf[3], gps = sg_.pf[4], gtx = sg_.pt[0], gty = sg_.pt[1];
+            const double s1e = sh.ls[cur][l1].e[i];
+            // partial sums of the row's block, M_{l1 l2} (6 values), and of the row's right-hand side, W_{l1} (3).  (The
+            // rhs lanes could take W through M's per-lane base and share its sums: 6 FP64 instructions less, but the
+            // static FP64 count of the loop body is how tests/test_se2_loop_mix.py sees that the arithmetic is untouched.)
+            const int mb = l1 == l2 ? (l1 == 0 ? 5 : 19) : 25, wb = l1 == 0 ? 2 : 16;
+            double mred[W][6], wred[W][3], bred[W][2];
+#pragma unroll
+            for (int o = 0; o < W; ++o) {
+#pragma unroll
+                for (int k = 0; k < 6; ++k) mred[o][k] = sh.red[o][mb + k];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) wred[o][k] = sh.red[o][wb + k];
+                bred[o][0] = sh.red[o][0]; bred[o][1] = sh.red[o][1];
+            }
+            const int lo_ = i < k3 ? i : k3, hi_ = i < k3 ? k3 : i;
+            const double sgv = sh.lc[l1].sg[lo_ * 3 - lo_ * (lo_ - 1) / 2 + (hi_ - lo_)];
+            // operands of the loops' own b^T H b term (lanes >= NL read loop 0's and drop the result)
+            const LoopConst& qq = sh.lc[lq_l];
+            const LoopState& sq = sh.ls[cur][lq_l];
+            const Pose2 qa{sq.pf[0], sq.pf[1], sq.pf[2], sq.pf[3], sq.pf[4]};
+            const Pose2 qb{sq.pt[0], sq.pt[1], sq.pt[2], sq.pt[3], sq.pt[4]};
+            const double qcz = qq.cz, qsz = qq.sz;
+            const Sym3 qom{qq.om[0], qq.om[1], qq.om[2], qq.om[3], qq.om[4], qq.om[5]};
+            double qv[2][3];
+#pragma unroll
+            for (int e = 0; e < 2; ++e)
+#pragma unroll
+                for (int k = 0; k < 3; ++k) qv[e][k] = sh.lvec[lq_l][e][k];
+            __builtin_amdgcn_sched_barrier(0);
+            // -- Gamma, and its entries to the lanes that use them: row i of loop l1 and row k3 of loop l2 for S[r][c],
+            // six cross-lane reads, one wait (nu's column of Gamma is fetched with mu, behind the pivots) --
+            double g1[3], g2[3], gam;
+            {
+                const double Aq = gpc * gcz - gps * gsz, Bq = gps * gcz + gpc * gsz;
+                const double Kx = -(gty - gauge.y), Ky = gtx - gauge.x;
+                gam = se2_gamma(Aq, Bq, Kx, Ky, gsig, g_i, g_a);
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    g1[a] = __shfl(gam, l1 * 9 + i * 3 + a, 64);
+                    g2[a] = __shfl(gam, l2 * 9 + k3 * 3 + a, 64);
                 }
             }
+            __builtin_amdgcn_sched_barrier(0);
+            // under them, independent of Gamma: the sums over the cell's waves and the loops' b^T H b term
+            double m[6], w[3];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                m[k] = mred[0][k];
+#pragma unroll
+                for (int o = 1; o < W; ++o) m[k] += mred[o][k];
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                w[k] = wred[0][k];
+#pragma unroll
+                for (int o = 1; o < W; ++o) w[k] += wred[o][k];
+            }
+            bb = bred[0][0];
+            bHb = bred[0][1];
+#pragma unroll
+            for (int o = 1; o < W; ++o) { bb += bred[o][0]; bHb += bred[o][1]; }
+            {
+                double wx, wy, wth;                        // (loop_quad)
+                se2_apply_J(qa, qb, qcz, qsz, qv[0][0], qv[0][1], qv[0][2], qv[1][0], qv[1][1], qv[1][2], wx, wy, wth);
+                const double lq = bl < NL ? qom.quad(wx, wy, wth) : 0.0;
+#pragma unroll
+                for (int l = 0; l < NL; ++l) bHb += read_lane(lq, l);
+            }
+            IPC_PIN2(bb, bHb);
+            __builtin_amdgcn_sched_barrier(0);
+            // -- assembly --
+            double val;
+            {
+                const double g10 = g1[0], g11 = g1[1], g12 = g1[2];
+                const double m00 = m[0], m01 = m[1], m02 = m[2], m11 = m[3], m12 = m[4], m22 = m[5];
+                const double t0 = g10 * m00 + g11 * m01 + g12 * m02;
+                const double t1 = g10 * m01 + g11 * m11 + g12 * m12;
+                const double t2 = g10 * m02 + g11 * m12 + g12 * m22;
+                double vS = t0 * g2[0] + t1 * g2[1] + t2 * g2[2];
+                const double vSd = vS + sgv;
+                vS = l1 == l2 ? vSd : vS;
+                const double vR = s1e - (g10 * w[0] + g11 * w[1] + g12 * w[2]);
+                val = c < NS ? vS : vR;
+                val = inS ? val : 0.0;
+            }
             bool okS = true;
+            alpha = 0.0; hsdNorm = 0.0;
 #pragma unroll
             for (int k = 0; k < NS; ++k) {
+                const double rowk = __shfl(val, k * RS + c, 64);
+                const double colk = __shfl(val, r * RS + k, 64);
+                __builtin_amdgcn_sched_barrier(0);         // the two cross-lane reads go first; the rest runs under them
                 const double piv = read_lane(val, k * RS + k);
                 okS = okS && (piv > 0);
                 double inv = __builtin_amdgcn_rcp(piv);
                 inv = fma(fma(-piv, inv, 1.0), inv, inv);
                 inv = fma(fma(-piv, inv, 1.0), inv, inv);
-                const double rowk = __shfl(val, k * RS + c, 64);
-                const double colk = __shfl(val, r * RS + k, 64);
+                // independent of the solve
+                if (k == 0) {
+                    alpha = bb / bHb;
+                    IPC_PIN1(alpha);
+                } else if (k == 1) {
+                    hsdNorm = sqrt(alpha * alpha * bb);
+                    IPC_PIN1(hsdNorm);
+                }
+                __builtin_amdgcn_sched_barrier(0);
                 val = (r == k) ? rowk * inv : fma(-(colk * rowk), inv, val);
             }
-            {   // nu_l[cc] = sum_rr Gamma_l[rr][cc] mu_{3l+rr}; mu_r sits in lane r*RS + NS
-                const int l = (lane < NS) ? lane / 3 : 0, cc = lane % 3;
-                double nv = 0.0;
+            {   // nu_l[cc] = sum_rr Gamma_l[rr][cc] mu_{3l+rr}; mu_r sits in lane r*RS + NS.  Formed in the lanes
+                // (row 3l, column cc).
+                double mu[3], gn[3];
 #pragma unroll
                 for (int rr = 0; rr < 3; ++rr) {
-                    const double mu_r = __shfl(val, (3 * l + rr) * RS + NS, 64);
-                    nv += gamw[l * 9 + rr * 3 + cc] * mu_r;
+                    mu[rr] = __shfl(val, (3 * l1 + rr) * RS + NS, 64);
+                    gn[rr] = __shfl(gam, l1 * 9 + rr * 3 + k3, 64);
                 }
+                double nv = 0.0;
 #pragma unroll
-                for (int l2 = 0; l2 < NL; ++l2)
+                for (int rr = 0; rr < 3; ++rr) nv += gn[rr] * mu[rr];
 #pragma unroll
-                    for (int k = 0; k < 3; ++k) nu[l2][k] = read_lane(nv, 3 * l2 + k);
-            }
-            bb = wtv(0);
-            bHb = wtv(1);
-            {
-                const double lq = lane < NL ? loop_quad(lane) : 0.0;
+                for (int l = 0; l < NL; ++l)
 #pragma unroll
-                for (int l = 0; l < NL; ++l) bHb += read_lane(lq, l);
+                    for (int k = 0; k < 3; ++k) nu[l][k] = read_lane(nv, 3 * l * RS + k);
             }
             if (!okS) { flags |= 2; break; }
-            alpha = bb / bHb;
-            hsdNorm = sqrt(alpha * alpha * bb);
         }
         IPC_WTICK(tmB2)
         // ---- phase C: u, rho, prefix sums -> h_gn; |h|^2, b.h (h^T H h = b.h) ----

@@ -50,9 +50,10 @@ def main():
         name = subprocess.run(["c++filt", r.get("name", "")], capture_output=True, text=True).stdout.strip()
         name = re.sub(r"\(.*", "", name)
         if pat in name:
-            print("%-46s vgpr %4s agpr %4s sgpr %4s lds %7s scratch %5s vspill %4s" % (
+            print("%-46s vgpr %4s agpr %4s sgpr %4s lds %7s scratch %5s vspill %4s sspill %4s" % (
                 name[-46:], r.get("vgpr_count"), r.get("agpr_count", "-"), r.get("sgpr_count"),
-                r.get("group_segment_fixed_size"), r.get("private_segment_fixed_size"), r.get("vgpr_spill_count")))
+                r.get("group_segment_fixed_size"), r.get("private_segment_fixed_size"), r.get("vgpr_spill_count"),
+                r.get("sgpr_spill_count", "-")))
 
 
 if __name__ == "__main__":
