@@ -340,6 +340,42 @@ typedef struct {
 int ipc_run_batch(ipc_engine_t* h, int n_runs, const int* run_offsets, const int* members, uint64_t* bits_out,
                   uint8_t* accepted_out, ipc_batch_report_t* report);
 
+/* ---- multi-start set maximisation -------------------------------------------------------------------
+ * ipc_set_max makes ONE greedy pass: the first live candidate of the processing order always joins, and an outlier whose own
+ * cell happens to pass vetoes every inlier it disagrees with.  ipc_set_max_multistart makes that pass from every live candidate
+ * and keeps the largest set.  Definition, over a matrix laid out as ipc_assemble_matrix writes it:
+ *   L = (l_0 .. l_{n-1}): the processing order (ipc_candidate_order) restricted to the live candidates, C[k][k] = 1.
+ *   S_q, for a seed position q: the greedy set over the sequence l_q, l_0, l_1, .., l_{q-1}, l_{q+1}, ..  -- a candidate joins
+ *     if it agrees with every member so far.  S_0 is exactly the set of ipc_set_max.
+ *   The result is the S_q of greatest cardinality, ties to the smallest q: never smaller than ipc_set_max's, pairwise
+ *     consistent, maximal (nobody outside agrees with every member), deterministic.  n = 0: the empty set.
+ *   sizes[k] = |S_q| for k = l_q, 0 for a candidate that is not live.
+ * Every live candidate is a seed (no pruning); this is not an exact maximum clique.
+ *
+ * ipc_set_max_multistart: device in, device out, enqueued on `stream`, no host synchronisation (as ipc_set_max).  Writes exactly
+ * d_accepted[0 .. N) (1 = in the set) and, unless NULL, d_sizes[0 .. N); reads d_bits only.  Errors as ipc_set_max: NULL h, d_bits
+ * or d_accepted: IPC_ERR_ARG; no candidates set: IPC_ERR_STATE; N beyond the LDS-resident mask: IPC_ERR_LIMIT -- the same N.
+ * The running intersection of a seed lives in registers while ceil(N/64) words are at most 64 x IPC_MULTISTART_REG_WORDS
+ * (<k> = 0, 1 or 2, default 2, read at ipc_create; 0 sends every N to the LDS kernel), in shared memory beyond; the outputs do
+ * not depend on the kernel.  The workspace (a compact copy of the matrix and four int vectors) belongs to the engine: a second
+ * call at the same N allocates nothing.
+ *
+ * ipc_run_multistart (one GPU): solve + assemble as ipc_run, then BOTH sets from the one matrix.  Host outputs, any may be NULL:
+ * bits_out [N][ceil(N/64)] and greedy_out [N] are bit for bit those of ipc_run on the same engine, accepted_out [N] and
+ * sizes_out [N] those of ipc_set_max_multistart.  The call enters matrix mode like every other matrix call and shares the cell
+ * buffers of ipc_solve_rows (ipc_cell_info describes its cells); the online matrix, the sweep's held first pass, the faithful
+ * state and the consensus set are neither read nor changed. */
+typedef struct {
+    int live;                 /* n: candidates whose own cell passed                                        */
+    int greedy_size;          /* |S_0|, the set of ipc_set_max                                              */
+    int best_size;            /* the multi-start set                                                        */
+    int best_seed;            /* its seed as a FILE index (-1: no live candidate)                           */
+    int best_seed_position;   /* ... and as a position q in L (-1: none)                                    */
+} ipc_multistart_report_t;
+int ipc_set_max_multistart(ipc_engine_t* h, const uint64_t* d_bits, uint8_t* d_accepted, int32_t* d_sizes, void* stream);
+int ipc_run_multistart(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accepted_out, uint8_t* greedy_out, int32_t* sizes_out,
+                       ipc_multistart_report_t* report);
+
 /* Diagnostics of the last ipc_solve_rows(), ipc_run_online(), ipc_run_sweep() or ipc_run_batch(): number of solved cells, and their records. */
 int ipc_cell_count(ipc_engine_t* h, int* n_cells);
 int ipc_cell_info(ipc_engine_t* h, ipc_cell_info_t* out, int capacity);

@@ -37,6 +37,7 @@ SYMBOLS = [
     "ipc_run_online", "ipc_online_covered", "ipc_online_reset", "ipc_reserve_candidates", "ipc_debug_live_resources",
     "ipc_run_sweep", "ipc_sweep_reset",
     "ipc_run_batch",
+    "ipc_set_max_multistart", "ipc_run_multistart",
 ]
 
 
@@ -81,6 +82,11 @@ class SweepReport(C.Structure):
 class BatchReport(C.Structure):
     _fields_ = [("runs", C.c_int), ("union_candidates", C.c_int), ("cells", C.c_int), ("cells_separate", C.c_longlong),
                 ("long_cells", C.c_int), ("damped_cells", C.c_int), ("literal_cells", C.c_int), ("chunks", C.c_int)]
+
+
+class MultistartReport(C.Structure):
+    _fields_ = [("live", C.c_int), ("greedy_size", C.c_int), ("best_size", C.c_int), ("best_seed", C.c_int),
+                ("best_seed_position", C.c_int)]
 
 
 CELL_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("lo", "<i4"), ("hi", "<i4"), ("max_chi2", "<f8"),
@@ -134,7 +140,9 @@ def load():
     lib.ipc_run_sweep.argtypes = [vp, ip, vp, vp, vp, vp, C.POINTER(SweepReport)]
     lib.ipc_sweep_reset.argtypes = [vp]
     lib.ipc_run_batch.argtypes = [vp, ip, vp, vp, vp, vp, C.POINTER(BatchReport)]
-    lib.ipc_run_sharded.argtypes = [C.POINTER(vp), ip, vp, vp]
+    lib.ipc_set_max_multistart.argtypes = [vp, vp, vp, vp, vp]
+    lib.ipc_run_multistart.argtypes = [vp, vp, vp, vp, vp, C.POINTER(MultistartReport)]
+    lib.ipc_run_sharded.argtypes =[C.POINTER(vp), ip, vp, vp]
     lib.ipc_run_set_only.argtypes = [vp, vp, C.POINTER(ip)]
     lib.ipc_cell_count.argtypes = [vp, C.POINTER(ip)]
     lib.ipc_cell_info.argtypes = [vp, vp, ip]

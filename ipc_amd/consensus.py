@@ -200,6 +200,21 @@ class IPC:
         mo = np.concatenate([[0], np.cumsum(mats)])
         return [bits[mo[q]:mo[q + 1]].reshape(sizes[q], -1) for q in range(len(runs))], accs, report
 
+    # ---- multi-start set maximisation: the greedy from every live seed, the largest set ----
+    def run_multistart(self, want_bits=False):
+        """ipc_run_multistart: solve and assemble as run(), then the greedy set of run() AND the multi-start set from the one
+        matrix.  Returns (accepted [N] uint8, greedy [N] uint8, sizes [N] int32, report dict), with want_bits
+        (bits [N, words] uint64, accepted, greedy, sizes, report); bits and greedy are those of run().  getMaxConsensusSet() is
+        left as it was."""
+        acc = np.zeros(self.N, dtype=np.uint8)
+        greedy = np.zeros(self.N, dtype=np.uint8)
+        sizes = np.zeros(self.N, dtype=np.int32)
+        bits = np.zeros((self.N, self.words), dtype=np.uint64) if want_bits else None
+        r = capi.MultistartReport()
+        capi.check(self.lib.ipc_run_multistart(self.h, _p(bits) if want_bits else None, _p(acc), _p(greedy), _p(sizes), C.byref(r)))
+        report = {k: getattr(r, k) for k, _ in capi.MultistartReport._fields_}
+        return (bits, acc, greedy, sizes, report) if want_bits else (acc, greedy, sizes, report)
+
     def consistency_matrix(self):
         bits, _ = self.run()
         return unpack_bits(bits, self.N)
@@ -284,6 +299,10 @@ class IPC:
     def set_max(self, d_bits_ptr, d_accepted_ptr, stream=0):
         capi.check(self.lib.ipc_set_max(self.h, C.c_void_p(d_bits_ptr), C.c_void_p(d_accepted_ptr),
                                         C.c_void_p(stream)))
+
+    def set_max_multistart(self, d_bits_ptr, d_accepted_ptr, d_sizes_ptr=0, stream=0):
+        capi.check(self.lib.ipc_set_max_multistart(self.h, C.c_void_p(d_bits_ptr), C.c_void_p(d_accepted_ptr),
+                                                   C.c_void_p(d_sizes_ptr) if d_sizes_ptr else None, C.c_void_p(stream)))
 
     # ---- diagnostics ----------------------------------------------------------------------
     def cell_info(self):

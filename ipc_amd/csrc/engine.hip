@@ -807,6 +807,12 @@ struct ipc_engine {
     PinnedBuf<unsigned long long> h_bt_stage; size_t bt_stage_cap = 0;   // in 8-byte words
     int batch_chunk = 0;                               // IPC_BATCH_CHUNK: cap on the runs per chunk (0: none)
     size_t batch_budget = 0;                           // IPC_BATCH_BUDGET: cap in bytes on a chunk's scratch (0: a quarter of the free memory alone)
+    // Multi-start set maximisation (ipc_set_max_multistart): the compact matrix P [N][words] over the live
+    // candidates, four int vectors [N] (live list, position map, |S_q| per seed position, ipc_run_multistart's sizes), the
+    // info words (multistart_kernels.hpp) and ipc_run_multistart's accepted bytes.
+    DevBuf<unsigned long long> d_ms_P; size_t ms_mat_cap = 0;
+    DevBuf<int> d_ms_vec, d_ms_info; DevBuf<unsigned char> d_ms_acc; int ms_vec_cap = 0;
+    int ms_reg_words = 2;                              // IPC_MULTISTART_REG_WORDS: most words of cand a lane keeps in registers (0: always the LDS kernel)
     // incremental mode / final map (SE2)
     std::vector<double> h_odom_meas, h_odom_info;      // file values, for the un-scaled chain
     std::vector<int> h_from, h_to, cns;
@@ -1112,6 +1118,7 @@ extern "C" int ipc_create(int dim, int n_vertices, const double* odom_meas, cons
     if (const char* sc = getenv("IPC_SWEEP_CHUNK")) { if (*sc) h->sweep_chunk = std::max(0, atoi(sc)); }
     if (const char* bc = getenv("IPC_BATCH_CHUNK")) { if (*bc) h->batch_chunk = std::max(0, atoi(bc)); }
     if (const char* bb = getenv("IPC_BATCH_BUDGET")) { if (*bb) h->batch_budget = (size_t)std::max(0ll, atoll(bb)); }
+    if (const char* mw = getenv("IPC_MULTISTART_REG_WORDS")) { if (*mw) h->ms_reg_words = std::min(2, std::max(0, atoi(mw))); }
     if (const char* sf = getenv("IPC_SLOW_FIRST")) { if (*sf) h->slow_first_iterations = std::max(0, atoi(sf)); }
     if (const char* rb = getenv("IPC_ROW_BALANCE")) {
         if (!strcmp(rb, "cyclic")) h->row_policy = 0;
@@ -1657,6 +1664,7 @@ __device__ __forceinline__ int slot_of_cell(const unsigned* slot_off, int nslots
 }
 #include "sweep_kernels.hpp"
 #include "batch_kernels.hpp"
+#include "multistart_kernels.hpp"
 // Failed cells -> list (host-driven Levenberg retry, rare); borderline cells -> the compact list of their slot (lit_cells /
 // lit_idx at the slot's own offset: a slot has room for all of its cells), counted per slot in recount[0 .. nslots).
 __global__ void k_collect_failed(int ncells, const int4* meta, const double* chi, const int2* cells, double fast_th,
@@ -2179,6 +2187,100 @@ extern "C" int ipc_run(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accepted_ou
     HIPCHK(hipStreamSynchronize(h->own_stream));
     if (bits_out) HIPCHK(hipMemcpy(bits_out, h->d_bits, sizeof(uint64_t) * need, hipMemcpyDeviceToHost));
     if (accepted_out) HIPCHK(hipMemcpy(accepted_out, h->d_acc, (size_t)N, hipMemcpyDeviceToHost));
+    return IPC_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// multi-start set maximisation: the greedy from every live seed, the largest set (multistart_kernels.hpp)
+// ------------------------------------------------------------------------------------------
+// workspace for N candidates: within what it holds a call allocates nothing
+static int ensure_multistart_scratch(ipc_engine* h, int N, size_t need)
+{
+    if (need > h->ms_mat_cap) {
+        h->ms_mat_cap = 0;
+        HIPCHK(h->d_ms_P.alloc(need));
+        h->ms_mat_cap = need;
+    }
+    if (N > h->ms_vec_cap) {
+        h->ms_vec_cap = 0;
+        HIPCHK(h->d_ms_vec.alloc(4 * (size_t)N));
+        HIPCHK(h->d_ms_acc.alloc((size_t)N));
+        h->ms_vec_cap = N;
+    }
+    if (!h->d_ms_info) HIPCHK(h->d_ms_info.alloc(kMsInfo));
+    return IPC_OK;
+}
+
+extern "C" int ipc_set_max_multistart(ipc_engine_t* h, const uint64_t* d_bits, uint8_t* d_accepted, int32_t* d_sizes, void* stream)
+{
+    if (!h || !d_bits || !d_accepted) return fail(IPC_ERR_ARG, "ipc_set_max_multistart: NULL argument");
+    if (h->N <= 0) return fail(IPC_ERR_STATE, "ipc_set_max_multistart: no candidates set");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->own_stream;
+    const int N = h->N, words = (N + 63) / 64;
+    const size_t row_bytes = sizeof(unsigned long long) * words;
+    if (row_bytes > 60 * 1024) return fail(IPC_ERR_LIMIT, "ipc_set_max_multistart: N=%d exceeds the LDS-resident mask", N);
+    if (int rc = matrix_mode_enter(h, st)) return rc;
+    if (int rc = ensure_multistart_scratch(h, N, (size_t)N * words)) return rc;
+    const int cap = h->ms_vec_cap;
+    int* live = h->d_ms_vec; int* pos = live + cap; int* sz = pos + cap;
+    const unsigned long long* C = (const unsigned long long*)d_bits;
+    hipLaunchKernelGGL(k_ms_live, dim3(1), dim3(1024), 0, st, N, words, (const int*)h->d_order, C, live, pos, h->d_ms_info);
+    const dim3 grid((N + kMsWaves - 1) / kMsWaves), block(64 * kMsWaves);
+    hipLaunchKernelGGL(k_ms_compact, grid, block, 0, st, words, C, (const int*)live, (const int*)h->d_ms_info, h->d_ms_P);
+    // cand in registers while a lane's share of the words is within the knob, else in LDS: as many waves per workgroup as
+    // 60 KB of slices hold, four at the most (one at the N limit)
+    const int per_lane = (words + 63) / 64;
+    if (per_lane <= h->ms_reg_words && per_lane == 1)
+        hipLaunchKernelGGL(k_ms_greedy_reg<1>, grid, block, 0, st, words, (const unsigned long long*)h->d_ms_P, (const int*)h->d_ms_info, sz);
+    else if (per_lane <= h->ms_reg_words)
+        hipLaunchKernelGGL(k_ms_greedy_reg<2>, grid, block, 0, st, words, (const unsigned long long*)h->d_ms_P, (const int*)h->d_ms_info, sz);
+    else {
+        const int wpb = (int)std::min<size_t>(kMsWaves, (60 * 1024) / row_bytes);
+        hipLaunchKernelGGL(k_ms_greedy_lds, dim3((N + wpb - 1) / wpb), dim3(64 * wpb), row_bytes * wpb, st, words, wpb,
+                           (const unsigned long long*)h->d_ms_P, (const int*)h->d_ms_info, sz);
+    }
+    hipLaunchKernelGGL(k_ms_pick, dim3(1), dim3(1024), row_bytes, st, N, words, (const unsigned long long*)h->d_ms_P, (const int*)live,
+                       (const int*)pos, (const int*)sz, h->d_ms_info, d_accepted, d_sizes);
+    HIPCHK(hipGetLastError());
+    return IPC_OK;
+}
+
+extern "C" int ipc_run_multistart(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accepted_out, uint8_t* greedy_out, int32_t* sizes_out,
+                                  ipc_multistart_report_t* report)
+{
+    if (!h) return fail(IPC_ERR_ARG, "ipc_run_multistart: NULL handle");
+    if (h->N <= 0) return fail(IPC_ERR_STATE, "ipc_run_multistart: no candidates set");
+    HIPCHK(hipSetDevice(h->device));
+    const int N = h->N, words = (N + 63) / 64;
+    const size_t need = (size_t)N * words;
+    if (sizeof(unsigned long long) * (size_t)words > 60 * 1024) return fail(IPC_ERR_LIMIT, "ipc_run_multistart: N=%d exceeds the LDS-resident mask", N);
+    if (int rc = ensure_run_scratch(h, N, need)) return rc;
+    if (int rc = ensure_multistart_scratch(h, N, need)) return rc;
+    int rc = ipc_solve_rows(h, 0, 1, h->d_upper, h->own_stream);
+    if (rc) return rc;
+    rc = ipc_assemble_matrix(h, h->d_upper, 1, h->d_bits, h->own_stream);
+    if (rc) return rc;
+    rc = ipc_set_max(h, h->d_bits, h->d_acc, h->own_stream);
+    if (rc) return rc;
+    int* d_sizes = h->d_ms_vec + 3 * (size_t)h->ms_vec_cap;
+    rc = ipc_set_max_multistart(h, h->d_bits, h->d_ms_acc, d_sizes, h->own_stream);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(h->own_stream));
+    if (bits_out) HIPCHK(hipMemcpy(bits_out, h->d_bits, sizeof(uint64_t) * need, hipMemcpyDeviceToHost));
+    if (accepted_out) HIPCHK(hipMemcpy(accepted_out, h->d_ms_acc, (size_t)N, hipMemcpyDeviceToHost));
+    if (greedy_out) HIPCHK(hipMemcpy(greedy_out, h->d_acc, (size_t)N, hipMemcpyDeviceToHost));
+    if (sizes_out) HIPCHK(hipMemcpy(sizes_out, d_sizes, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost));
+    if (report) {
+        int info[kMsInfo];
+        std::vector<unsigned char> greedy((size_t)N);
+        HIPCHK(hipMemcpy(info, h->d_ms_info, sizeof(info), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(greedy.data(), h->d_acc, (size_t)N, hipMemcpyDeviceToHost));
+        int g = 0;
+        for (unsigned char a : greedy) g += a ? 1 : 0;
+        report->live = info[0]; report->greedy_size = g; report->best_size = info[1];
+        report->best_seed = info[3]; report->best_seed_position = info[2];
+    }
     return IPC_OK;
 }
 
