@@ -376,6 +376,49 @@ int ipc_set_max_multistart(ipc_engine_t* h, const uint64_t* d_bits, uint8_t* d_a
 int ipc_run_multistart(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accepted_out, uint8_t* greedy_out, int32_t* sizes_out,
                        ipc_multistart_report_t* report);
 
+/* ---- exact maximum consistent set ---------------------------------------------------------------------
+ * ipc_set_max and ipc_set_max_multistart return consistent sets without saying how far they are from the largest one.
+ * ipc_set_max_exact searches for it, within a budget, and says what it proved.  Definition, over a matrix laid out as
+ * ipc_assemble_matrix writes it:
+ *   L = (l_0 .. l_{n-1}): the processing order (ipc_candidate_order) restricted to the live candidates, C[k][k] = 1.
+ *   G: the graph on L whose edges are the set off-diagonal bits.  omega: its clique number.
+ *   LB: the size of the set of ipc_set_max_multistart on the same matrix.
+ *   UB0: the number of colours of the sequential greedy colouring of L in position order -- repeat: open a colour class, sweep
+ *     the uncoloured positions in ascending order, take a position if it is adjacent to no member of the class.
+ *   The work is split into independent subproblems, one per position q: the cliques whose smallest position is q, with the
+ *     candidate set N(l_q) restricted to the positions > q.  A subproblem whose 1 + |candidate set| <= LB is pruned at once;
+ *     every other one is a depth-first branch-and-bound with a greedy colouring bound at every node, pruned against LB and
+ *     against its OWN finds only (size + colour <= best).  A step is one row of the compact matrix fetched and combined; a
+ *     subproblem gives up after IPC_EXACT_STEP_CAP steps (read at ipc_create, default 2^20, clamped to [1, 2^30]).
+ *   Every subproblem finishes (or LB = UB0 and none is needed): proven = 1, size = upper_bound = omega and the set is a maximum
+ *     clique -- the multi-start set, byte for byte, if omega = LB, else the clique of the smallest q that attains omega, and
+ *     within that subproblem the first clique of that size in the search's own fixed order (NOT the lexicographically first
+ *     maximum clique).  Some subproblem hits the cap: proven = 0, the set is the multi-start set, size = LB, upper_bound = UB0.
+ *     n = 0: the empty set, proven = 1, size = upper_bound = 0.
+ *   No subproblem reads another one's progress, so which subproblems are capped, steps, size, proven and the set are pure
+ *     functions of the matrix, the order and the cap: identical from run to run, whatever wave runs what.
+ *
+ * ipc_set_max_exact: device in, device out, on `stream` -- but it BLOCKS THE HOST: it reads n, LB and UB0 back to size its
+ * workspace, waits for the search and returns with the report filled.  Writes exactly d_accepted[0 .. N) (1 = in the set), reads
+ * d_bits only; `report` may be NULL.  Errors as ipc_set_max_multistart: NULL h, d_bits or d_accepted: IPC_ERR_ARG; no candidates
+ * set: IPC_ERR_STATE; N > 8192 (a row of the compact matrix is at most two words per lane): IPC_ERR_LIMIT, before anything is
+ * allocated.  The depth-first stacks (min(UB0, n) levels for each wave of a pool) belong to the engine and are reused at the
+ * same size; a call whose stacks would exceed a quarter of the free device memory returns IPC_ERR_LIMIT before allocating them.
+ *
+ * ipc_run_exact (one GPU): solve + assemble as ipc_run, then the multi-start and the exact set from the one matrix.  Host
+ * outputs, any may be NULL: bits_out [N][ceil(N/64)] is bit for bit that of ipc_run, multistart_out [N] the accepted_out of
+ * ipc_run_multistart, accepted_out [N] the set of ipc_set_max_exact.  The call enters matrix mode like every other matrix call
+ * and shares the cell buffers of ipc_solve_rows; the online matrix, the sweep's held first pass, the faithful state and the
+ * consensus set are neither read nor changed. */
+typedef struct {
+    int live, multistart_size, size, upper_bound, proven;
+    int subproblems;          /* subproblems whose root was not pruned at once */
+    int capped;               /* subproblems that hit the step cap */
+    long long steps;          /* row loads over all subproblems */
+} ipc_exact_report_t;
+int ipc_set_max_exact(ipc_engine_t* h, const uint64_t* d_bits, uint8_t* d_accepted, ipc_exact_report_t* report, void* stream);
+int ipc_run_exact(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accepted_out, uint8_t* multistart_out, ipc_exact_report_t* report);
+
 /* Diagnostics of the last ipc_solve_rows(), ipc_run_online(), ipc_run_sweep() or ipc_run_batch(): number of solved cells, and their records. */
 int ipc_cell_count(ipc_engine_t* h, int* n_cells);
 int ipc_cell_info(ipc_engine_t* h, ipc_cell_info_t* out, int capacity);

@@ -38,6 +38,7 @@ SYMBOLS = [
     "ipc_run_sweep", "ipc_sweep_reset",
     "ipc_run_batch",
     "ipc_set_max_multistart", "ipc_run_multistart",
+    "ipc_set_max_exact", "ipc_run_exact",
 ]
 
 
@@ -87,6 +88,11 @@ class BatchReport(C.Structure):
 class MultistartReport(C.Structure):
     _fields_ = [("live", C.c_int), ("greedy_size", C.c_int), ("best_size", C.c_int), ("best_seed", C.c_int),
                 ("best_seed_position", C.c_int)]
+
+
+class ExactReport(C.Structure):
+    _fields_ = [("live", C.c_int), ("multistart_size", C.c_int), ("size", C.c_int), ("upper_bound", C.c_int),
+                ("proven", C.c_int), ("subproblems", C.c_int), ("capped", C.c_int), ("steps", C.c_longlong)]
 
 
 CELL_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("lo", "<i4"), ("hi", "<i4"), ("max_chi2", "<f8"),
@@ -142,6 +148,8 @@ def load():
     lib.ipc_run_batch.argtypes = [vp, ip, vp, vp, vp, vp, C.POINTER(BatchReport)]
     lib.ipc_set_max_multistart.argtypes = [vp, vp, vp, vp, vp]
     lib.ipc_run_multistart.argtypes = [vp, vp, vp, vp, vp, C.POINTER(MultistartReport)]
+    lib.ipc_set_max_exact.argtypes = [vp, vp, vp, C.POINTER(ExactReport), vp]
+    lib.ipc_run_exact.argtypes = [vp, vp, vp, vp, C.POINTER(ExactReport)]
     lib.ipc_run_sharded.argtypes =[C.POINTER(vp), ip, vp, vp]
     lib.ipc_run_set_only.argtypes = [vp, vp, C.POINTER(ip)]
     lib.ipc_cell_count.argtypes = [vp, C.POINTER(ip)]

@@ -215,6 +215,20 @@ class IPC:
         report = {k: getattr(r, k) for k, _ in capi.MultistartReport._fields_}
         return (bits, acc, greedy, sizes, report) if want_bits else (acc, greedy, sizes, report)
 
+    # ---- exact maximum consistent set: branch-and-bound with the multi-start set as the lower bound ----
+    def run_exact(self, want_bits=False):
+        """ipc_run_exact: solve and assemble as run(), then the multi-start set AND the exact set from the one matrix.  Returns
+        (accepted [N] uint8, multistart [N] uint8, report dict), with want_bits (bits [N, words] uint64, accepted, multistart,
+        report).  report["proven"] = 1: accepted is a maximum consistent set of report["size"] members; 0: accepted is the
+        multi-start set and the optimum lies in [size, upper_bound].  getMaxConsensusSet() is left as it was."""
+        acc = np.zeros(self.N, dtype=np.uint8)
+        ms = np.zeros(self.N, dtype=np.uint8)
+        bits = np.zeros((self.N, self.words), dtype=np.uint64) if want_bits else None
+        r = capi.ExactReport()
+        capi.check(self.lib.ipc_run_exact(self.h, _p(bits) if want_bits else None, _p(acc), _p(ms), C.byref(r)))
+        report = {k: getattr(r, k) for k, _ in capi.ExactReport._fields_}
+        return (bits, acc, ms, report) if want_bits else (acc, ms, report)
+
     def consistency_matrix(self):
         bits, _ = self.run()
         return unpack_bits(bits, self.N)
@@ -303,6 +317,12 @@ class IPC:
     def set_max_multistart(self, d_bits_ptr, d_accepted_ptr, d_sizes_ptr=0, stream=0):
         capi.check(self.lib.ipc_set_max_multistart(self.h, C.c_void_p(d_bits_ptr), C.c_void_p(d_accepted_ptr),
                                                    C.c_void_p(d_sizes_ptr) if d_sizes_ptr else None, C.c_void_p(stream)))
+
+    def set_max_exact(self, d_bits_ptr, d_accepted_ptr, stream=0):
+        """ipc_set_max_exact on device pointers; blocks until the search is over and returns the report as a dict."""
+        r = capi.ExactReport()
+        capi.check(self.lib.ipc_set_max_exact(self.h, C.c_void_p(d_bits_ptr), C.c_void_p(d_accepted_ptr), C.byref(r), C.c_void_p(stream)))
+        return {k: getattr(r, k) for k, _ in capi.ExactReport._fields_}
 
     # ---- diagnostics ----------------------------------------------------------------------
     def cell_info(self):

@@ -813,6 +813,13 @@ struct ipc_engine {
     DevBuf<unsigned long long> d_ms_P; size_t ms_mat_cap = 0;
     DevBuf<int> d_ms_vec, d_ms_info; DevBuf<unsigned char> d_ms_acc; int ms_vec_cap = 0;
     int ms_reg_words = 2;                              // IPC_MULTISTART_REG_WORDS: most words of cand a lane keeps in registers (0: always the LDS kernel)
+    // Exact maximum consistent set (ipc_set_max_exact), over the multi-start's P: the info words
+    // (exact_kernels.hpp), three int vectors [N] (flag, size and steps by subproblem), the depth-first stacks of the wave pool
+    // (8-byte words) and the clique of every subproblem (16-bit positions, [n][levels]).
+    DevBuf<int> d_ex_info, d_ex_vec; int ex_vec_cap = 0;
+    DevBuf<unsigned long long> d_ex_ws; size_t ex_ws_cap = 0;
+    DevBuf<unsigned short> d_ex_clq; size_t ex_clq_cap = 0;
+    unsigned ex_step_cap = 1u << 20;                   // IPC_EXACT_STEP_CAP: steps after which a subproblem gives up
     // incremental mode / final map (SE2)
     std::vector<double> h_odom_meas, h_odom_info;      // file values, for the un-scaled chain
     std::vector<int> h_from, h_to, cns;
@@ -1119,6 +1126,7 @@ extern "C" int ipc_create(int dim, int n_vertices, const double* odom_meas, cons
     if (const char* bc = getenv("IPC_BATCH_CHUNK")) { if (*bc) h->batch_chunk = std::max(0, atoi(bc)); }
     if (const char* bb = getenv("IPC_BATCH_BUDGET")) { if (*bb) h->batch_budget = (size_t)std::max(0ll, atoll(bb)); }
     if (const char* mw = getenv("IPC_MULTISTART_REG_WORDS")) { if (*mw) h->ms_reg_words = std::min(2, std::max(0, atoi(mw))); }
+    if (const char* ec = getenv("IPC_EXACT_STEP_CAP")) { if (*ec) h->ex_step_cap = (unsigned)std::min(1ll << 30, std::max(1ll, atoll(ec))); }
     if (const char* sf = getenv("IPC_SLOW_FIRST")) { if (*sf) h->slow_first_iterations = std::max(0, atoi(sf)); }
     if (const char* rb = getenv("IPC_ROW_BALANCE")) {
         if (!strcmp(rb, "cyclic")) h->row_policy = 0;
@@ -1665,6 +1673,7 @@ __device__ __forceinline__ int slot_of_cell(const unsigned* slot_off, int nslots
 #include "sweep_kernels.hpp"
 #include "batch_kernels.hpp"
 #include "multistart_kernels.hpp"
+#include "exact_kernels.hpp"
 // Failed cells -> list (host-driven Levenberg retry, rare); borderline cells -> the compact list of their slot (lit_cells /
 // lit_idx at the slot's own offset: a slot has room for all of its cells), counted per slot in recount[0 .. nslots).
 __global__ void k_collect_failed(int ncells, const int4* meta, const double* chi, const int2* cells, double fast_th,
@@ -2281,6 +2290,117 @@ extern "C" int ipc_run_multistart(ipc_engine_t* h, uint64_t* bits_out, uint8_t* 
         report->live = info[0]; report->greedy_size = g; report->best_size = info[1];
         report->best_seed = info[3]; report->best_seed_position = info[2];
     }
+    return IPC_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// exact maximum consistent set: branch-and-bound over the multi-start's compact matrix (exact_kernels.hpp)
+// ------------------------------------------------------------------------------------------
+constexpr int kExLimitN = 8192;                        // a row of the compact matrix is at most two words per lane
+constexpr int kExPool = 2048, kExPoolFloor = 256;      // waves of k_ex_search: as many as subproblems up to kExPool, halved
+constexpr size_t kExPoolBytes = (size_t)2 << 30;       // ... down to kExPoolFloor while their stacks exceed this
+
+// The multi-start set into d_accepted, UB0, then -- unless that already closes the bracket -- the search and the pick.  Blocks the
+// host twice: once to size the workspace from n, LB and UB0, once for the report.  ms_host, unless NULL, gets the multi-start set.
+static int set_max_exact(ipc_engine* h, const uint64_t* d_bits, uint8_t* d_accepted, ipc_exact_report_t* report, hipStream_t st,
+                         uint8_t* ms_host)
+{
+    const int N = h->N, words = (N + 63) / 64;
+    if (int rc = ipc_set_max_multistart(h, d_bits, d_accepted, nullptr, st)) return rc;
+    if (N > h->ex_vec_cap) {
+        h->ex_vec_cap = 0;
+        HIPCHK(h->d_ex_vec.alloc(3 * (size_t)N));
+        h->ex_vec_cap = N;
+    }
+    if (!h->d_ex_info) HIPCHK(h->d_ex_info.alloc(kExInfo));
+    const unsigned long long* P = h->d_ms_P;
+    const int* ms_info = h->d_ms_info;
+    const bool one = words <= 64;
+    if (one) hipLaunchKernelGGL(k_ex_bound<1>, dim3(1), dim3(64), 0, st, words, P, ms_info, (int*)h->d_ex_info);
+    else hipLaunchKernelGGL(k_ex_bound<2>, dim3(1), dim3(64), 0, st, words, P, ms_info, (int*)h->d_ex_info);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    int ms[kMsInfo], ex[kExInfo] = {0};
+    HIPCHK(hipMemcpy(ms, h->d_ms_info, sizeof(ms), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ex, h->d_ex_info, sizeof(int), hipMemcpyDeviceToHost));
+    if (ms_host) HIPCHK(hipMemcpy(ms_host, d_accepted, (size_t)N, hipMemcpyDeviceToHost));
+    const int n = ms[0], lb = ms[1], ub0 = ex[0];
+    ipc_exact_report_t rep{};
+    rep.live = n; rep.multistart_size = lb; rep.size = lb; rep.upper_bound = ub0; rep.proven = lb >= ub0 ? 1 : 0;
+    if (lb < ub0) {
+        const int levels = std::min(ub0, n);
+        const int level_words = 64 * (one ? 1 : 2) + (n + 3) / 4 + 1;
+        const size_t slice_words = (size_t)levels * level_words + (size_t)(levels + 1) / 2;
+        int pool = std::min(kExPool, (n + kExWaves - 1) / kExWaves * kExWaves);
+        while (pool > kExPoolFloor && pool * slice_words * 8 > kExPoolBytes) pool /= 2;
+        const size_t need_ws = pool * slice_words, need_clq = (size_t)n * levels;
+        if (need_ws > h->ex_ws_cap || need_clq > h->ex_clq_cap) {
+            size_t mem_free = 0, mem_total = 0;
+            HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
+            const size_t bytes = (need_ws > h->ex_ws_cap ? need_ws * 8 : 0) + (need_clq > h->ex_clq_cap ? need_clq * 2 : 0);
+            if (bytes > mem_free / 4)
+                return fail(IPC_ERR_LIMIT, "ipc_set_max_exact: a search of %d levels over %d live candidates needs %zu MB, a quarter of the free memory is %zu MB",
+                            levels, n, bytes >> 20, mem_free >> 22);
+        }
+        if (need_ws > h->ex_ws_cap) {
+            h->ex_ws_cap = 0;
+            HIPCHK(h->d_ex_ws.alloc(need_ws));
+            h->ex_ws_cap = need_ws;
+        }
+        if (need_clq > h->ex_clq_cap) {
+            h->ex_clq_cap = 0;
+            HIPCHK(h->d_ex_clq.alloc(need_clq));
+            h->ex_clq_cap = need_clq;
+        }
+        const int cap = h->ex_vec_cap;
+        int* flag = h->d_ex_vec; int* size = flag + cap; unsigned* steps = (unsigned*)(size + cap);
+        const dim3 grid(pool / kExWaves), block(64 * kExWaves);
+        if (one)
+            hipLaunchKernelGGL(k_ex_search<1>, grid, block, 0, st, words, levels, level_words, slice_words, h->ex_step_cap, P, ms_info,
+                               (int*)h->d_ex_info, (unsigned long long*)h->d_ex_ws, flag, size, steps, (unsigned short*)h->d_ex_clq);
+        else
+            hipLaunchKernelGGL(k_ex_search<2>, grid, block, 0, st, words, levels, level_words, slice_words, h->ex_step_cap, P, ms_info,
+                               (int*)h->d_ex_info, (unsigned long long*)h->d_ex_ws, flag, size, steps, (unsigned short*)h->d_ex_clq);
+        hipLaunchKernelGGL(k_ex_pick, dim3(1), dim3(1024), 0, st, N, levels, (const int*)h->d_ms_vec, ms_info, (const int*)flag,
+                           (const int*)size, (const unsigned*)steps, (const unsigned short*)h->d_ex_clq, (int*)h->d_ex_info, d_accepted);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpy(ex, h->d_ex_info, sizeof(ex), hipMemcpyDeviceToHost));
+        rep.subproblems = ex[4]; rep.capped = ex[5];
+        rep.steps = (long long)(((unsigned long long)(unsigned)ex[7] << 32) | (unsigned)ex[6]);
+        if (rep.capped == 0) { rep.proven = 1; rep.size = rep.upper_bound = ex[2]; }
+    }
+    if (report) *report = rep;
+    return IPC_OK;
+}
+
+extern "C" int ipc_set_max_exact(ipc_engine_t* h, const uint64_t* d_bits, uint8_t* d_accepted, ipc_exact_report_t* report, void* stream)
+{
+    if (!h || !d_bits || !d_accepted) return fail(IPC_ERR_ARG, "ipc_set_max_exact: NULL argument");
+    if (h->N <= 0) return fail(IPC_ERR_STATE, "ipc_set_max_exact: no candidates set");
+    if (h->N > kExLimitN) return fail(IPC_ERR_LIMIT, "ipc_set_max_exact: N=%d exceeds %d candidates", h->N, kExLimitN);
+    HIPCHK(hipSetDevice(h->device));
+    return set_max_exact(h, d_bits, d_accepted, report, stream ? (hipStream_t)stream : h->own_stream, nullptr);
+}
+
+extern "C" int ipc_run_exact(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accepted_out, uint8_t* multistart_out, ipc_exact_report_t* report)
+{
+    if (!h) return fail(IPC_ERR_ARG, "ipc_run_exact: NULL handle");
+    if (h->N <= 0) return fail(IPC_ERR_STATE, "ipc_run_exact: no candidates set");
+    if (h->N > kExLimitN) return fail(IPC_ERR_LIMIT, "ipc_run_exact: N=%d exceeds %d candidates", h->N, kExLimitN);
+    HIPCHK(hipSetDevice(h->device));
+    const int N = h->N, words = (N + 63) / 64;
+    const size_t need = (size_t)N * words;
+    if (int rc = ensure_run_scratch(h, N, need)) return rc;
+    if (int rc = ensure_multistart_scratch(h, N, need)) return rc;
+    int rc = ipc_solve_rows(h, 0, 1, h->d_upper, h->own_stream);
+    if (rc) return rc;
+    rc = ipc_assemble_matrix(h, h->d_upper, 1, h->d_bits, h->own_stream);
+    if (rc) return rc;
+    rc = set_max_exact(h, h->d_bits, h->d_ms_acc, report, h->own_stream, multistart_out);
+    if (rc) return rc;
+    if (bits_out) HIPCHK(hipMemcpy(bits_out, h->d_bits, sizeof(uint64_t) * need, hipMemcpyDeviceToHost));
+    if (accepted_out) HIPCHK(hipMemcpy(accepted_out, h->d_ms_acc, (size_t)N, hipMemcpyDeviceToHost));
     return IPC_OK;
 }
 

@@ -64,6 +64,10 @@ class EngineBackend:
         """The multi-start set (ipc_set_max_multistart): accepted [N] uint8, sizes [N] int32 or None."""
         self.e.set_max_multistart(bits.data_ptr(), accepted.data_ptr(), 0 if sizes is None else sizes.data_ptr(), self._stream())
 
+    def set_max_exact(self, bits, accepted):
+        """The exact set or its bracket (ipc_set_max_exact): accepted [N] uint8; blocks the host, returns the report dict."""
+        return self.e.set_max_exact(bits.data_ptr(), accepted.data_ptr(), self._stream())
+
 
 class ShardedMatrix:
     def __init__(self, backend, rank=0, world=1, group=None, force_gather=False):
