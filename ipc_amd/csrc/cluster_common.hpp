@@ -96,6 +96,9 @@ struct ClusterOut {
     int iterations = 0, tries = 0, flags = 0, evals = 0;    // flags: 1 terminated, 2 solve failed
 };
 
+// Poses of either type as the host passes them around: device rows of one block, row r at p + r * ld
+// (SE2: x y th cos sin, SE3: R row-major (9), t (3)).
+struct PoseBlock { double* p; int ld; };
 
 // Loop tables of a cluster in one int array (host layout == device layout):
 //   lfrom[nl] lto[nl] lcand[nl]  local end points / candidate record index
@@ -234,11 +237,6 @@ inline PoseBandPlan pose_band_plan(int d, int L, int nl, const int* lf, const in
     P.use = P.nbp >= 1 && wd * 3.0 <= (double)d * L;         // (a third of the dense width at most: otherwise the dense store)
     return P;
 }
-
-struct LiteralBand;                                         // cluster_literal_band.hpp
-inline void literal_band_free(LiteralBand* p);
-template <class Solver>
-hipError_t literal_band_damped(Solver& S, double lambda, bool& used, double* x_out, int* d_info);
 
 // Ops:  evaluate_committed(chi) | linearize(bb, bHb, hh, bh, info) | blend(alpha, c, bma)
 //       | trial(p, q, newChi, anyChanged) | commit() | max_edge_chi2(mx)

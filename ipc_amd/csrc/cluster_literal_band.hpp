@@ -20,7 +20,6 @@ struct LiteralBand {
     DevBuf<double> d_zero;
     long solves = 0;
 };
-inline void literal_band_free(LiteralBand* p) { delete p; }
 
 inline hipError_t band_system_solve(const BandLayout& B, double* A, double* Lf, double* dinv, double* x, PersistCtl* ctl, int* info,
                                     const double* zero, int workgroups, hipStream_t st)
@@ -53,7 +52,7 @@ hipError_t literal_band_damped(Solver& S, double lambda, bool& used, double* x_o
 {
     constexpr int d = Solver::kD;
     used = false;
-    if (!S.lband) S.lband = new LiteralBand();
+    if (!S.lband) S.lband.reset(new LiteralBand());
     LiteralBand& W = *S.lband;
     const LoopTables& T = S.tables();
     const int L = T.L, nl = T.nl;
@@ -105,8 +104,5 @@ hipError_t literal_band_damped(Solver& S, double lambda, bool& used, double* x_o
     used = true;
     return hipSuccess;
 }
-
-inline long ClusterSolver2::literal_band_solves() const { return lband ? lband->solves : 0; }
-inline long ClusterSolver3::literal_band_solves() const { return lband ? lband->solves : 0; }
 
 }  // namespace ipc

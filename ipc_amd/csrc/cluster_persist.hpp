@@ -713,116 +713,6 @@ __global__ __launch_bounds__(kPT, 1) void pchol_test_kernel(double* A, double* L
     }
 }
 
-// ---- pose-type bindings -------------------------------------------------------------------------------------
-struct PersistSe2 {
-    using Dev = ClusterDev;
-    static constexpr int kD = 3, kNPS = 9, kNND = 3, kSC1 = 1, kSC2 = 2;
-    static constexpr int kEdgeDoubles = 43, kLoopDoubles = 27;          // per ld / per loop, + (ld + nl) of chi_edges
-    __device__ static void load_initial(const Dev& D, const double* src, int V, int i)
-    {
-        const size_t s = (size_t)D.lo + i;
-        auto g = gptr(src);
-        gptr(D.X.x)[i] = g[s]; gptr(D.X.y)[i] = g[(size_t)V + s]; gptr(D.X.th)[i] = g[2 * (size_t)V + s];
-        gptr(D.X.c)[i] = g[3 * (size_t)V + s]; gptr(D.X.s)[i] = g[4 * (size_t)V + s];
-    }
-    __device__ static void eval(const Dev& D, bool trial, int i, double (&v)[1])
-    {
-        if (trial) gk_eval_at(D, D.Xn, D.en, D.len, i, v); else gk_eval_at(D, D.X, D.e, D.le, i, v);
-    }
-    __device__ static void chi_edges(const Dev& D, int i) { gk_chi_edges_at(D, i); }
-    __device__ static void force(const Dev& D, int i) { gk_force_at(D, i); }
-    __device__ static void b(const Dev& D, int i, double (&v)[1]) { gk_b_at(D, i, v); }
-    __device__ static void bHb_psi(const Dev& D, int i, double (&v)[1]) { gk_bHb_psi_at(D, i, v); }
-    __device__ static void assemble(const Dev& D, int l1, int l2) { gk_assemble_at(D, l1, l2); }
-    template <class Put, class PutRhs>
-    __device__ static void assemble_core(const Dev& D, int l1, int l2, Put put, PutRhs put_rhs) { gk_assemble_core(D, l1, l2, put, put_rhs); }
-    // the banded kernel's unit of assembly work: the whole 3 x 3 block
-    static constexpr int kAsmRows = 1;
-    template <class Put, class PutRhs>
-    __device__ static void assemble_row(const Dev& D, int l1, int l2, int, Put put, PutRhs put_rhs) { gk_assemble_core(D, l1, l2, put, put_rhs); }
-    __device__ static void nu(const Dev& D, int l) { gk_nu_at(D, l); }
-    __device__ static void events(const Dev& D, int j) { gk_events_at(D, j); }
-    __device__ static void rho(const Dev& D, int i) { gk_rho_at(D, i); }
-    __device__ static void term(const Dev& D, int i) { gk_term_at(D, i); }
-    __device__ static void h(const Dev& D, int i, double (&v)[2]) { gk_h_at(D, i, v); }
-    __device__ static void blend(const Dev& D, double alpha, int i, double (&v)[2]) { gk_blend_at(D, alpha, i, v); }
-    __device__ static void update(const Dev& D, double p, double q, int i, double (&v)[1]) { gk_update_at(D, p, q, i, v); }
-    static void exchange(Dev& D)                 // the view after a commit: committed <-> trial buffers
-    {
-        PoseArr tx = D.X; D.X = D.Xn; D.Xn = tx;
-        double* t = D.e; D.e = D.en; D.en = t;
-        t = D.le; D.le = D.len; D.len = t;
-    }
-    static void carve(Dev& D, double* edge, double* loop, int ld, int nl)
-    {
-        double* p = edge;
-        auto take = [&](size_t n) { double* q = p; p += n; return q; };
-        D.X = PoseArr{take(ld), take(ld), take(ld), take(ld), take(ld)};
-        D.Xn = PoseArr{take(ld), take(ld), take(ld), take(ld), take(ld)};
-        D.e = take(3 * (size_t)ld); D.en = take(3 * (size_t)ld); D.g = take(3 * (size_t)ld); D.m = take(3 * (size_t)ld);
-        D.b = take(3 * (size_t)ld); D.h = take(3 * (size_t)ld); D.ps = take(9 * (size_t)ld); D.nd = take(3 * (size_t)ld);
-        D.sc = take(3 * (size_t)ld);
-        D.chi_edges = take((size_t)ld + nl);
-        double* q = loop;
-        auto takel = [&](size_t n) { double* r = q; q += n; return r; };
-        D.le = takel(3 * (size_t)nl); D.len = takel(3 * (size_t)nl); D.lg = takel(3 * (size_t)nl); D.lm = takel(3 * (size_t)nl);
-        D.gam = takel(9 * (size_t)nl); D.nu = takel(3 * (size_t)nl); D.rhs = takel(3 * (size_t)nl);
-    }
-};
-
-struct PersistSe3 {
-    using Dev = ClusterDev3;
-    static constexpr int kD = 6, kNPS = 27, kNND = 6, kSC1 = 3, kSC2 = 3;
-    static constexpr int kEdgeDoubles = 99, kLoopDoubles = 72;
-    __device__ static void load_initial(const Dev& D, const double* src, int src_ld, int i)
-    {
-#pragma unroll
-        for (int k = 0; k < 12; ++k) D.X[(size_t)k * D.ld + i] = src[(size_t)k * src_ld + D.lo + i];
-    }
-    __device__ static void eval(const Dev& D, bool trial, int i, double (&v)[1])
-    {
-        if (trial) gk3_eval_at(D, D.Xn, D.en, D.len, i, v); else gk3_eval_at(D, D.X, D.e, D.le, i, v);
-    }
-    __device__ static void chi_edges(const Dev& D, int i) { gk3_chi_edges_at(D, i); }
-    __device__ static void force(const Dev& D, int i) { gk3_force_at(D, i); }
-    __device__ static void b(const Dev& D, int i, double (&v)[1]) { gk3_b_at(D, i, v); }
-    __device__ static void bHb_psi(const Dev& D, int i, double (&v)[1]) { gk3_bHb_psi_at(D, i, v); }
-    __device__ static void assemble(const Dev& D, int l1, int l2) { gk3_assemble_at(D, l1, l2); }
-    template <class Put, class PutRhs>
-    __device__ static void assemble_core(const Dev& D, int l1, int l2, Put put, PutRhs put_rhs) { gk3_assemble_core(D, l1, l2, put, put_rhs); }
-    // the banded kernel's unit of assembly work: one row of a 6 x 6 block
-    static constexpr int kAsmRows = 6;
-    template <class Put, class PutRhs>
-    __device__ static void assemble_row(const Dev& D, int l1, int l2, int r, Put put, PutRhs put_rhs) { gk3_assemble_row(D, l1, l2, r, put, put_rhs); }
-    __device__ static void nu(const Dev& D, int l) { gk3_nu_at(D, l); }
-    __device__ static void events(const Dev& D, int j) { gk3_events_at(D, j); }
-    __device__ static void rho(const Dev& D, int i) { gk3_rho_at(D, i); }
-    __device__ static void term(const Dev& D, int i) { gk3_term_at(D, i); }
-    __device__ static void h(const Dev& D, int i, double (&v)[2]) { gk3_h_at(D, i, v); }
-    __device__ static void blend(const Dev& D, double alpha, int i, double (&v)[2]) { gk3_blend_at(D, alpha, i, v); }
-    __device__ static void update(const Dev& D, double p, double q, int i, double (&v)[1]) { gk3_update_at(D, p, q, i, v); }
-    static void exchange(Dev& D)                 // the view after a commit: committed <-> trial buffers
-    {
-        double* t = D.X; D.X = D.Xn; D.Xn = t;
-        t = D.e; D.e = D.en; D.en = t;
-        t = D.le; D.le = D.len; D.len = t;
-    }
-    static void carve(Dev& D, double* edge, double* loop, int ld, int nl)
-    {
-        double* p = edge;
-        auto take = [&](size_t n) { double* q = p; p += n; return q; };
-        D.X = take(12 * (size_t)ld); D.Xn = take(12 * (size_t)ld);
-        D.e = take(6 * (size_t)ld); D.en = take(6 * (size_t)ld); D.g = take(6 * (size_t)ld); D.m = take(6 * (size_t)ld);
-        D.b = take(6 * (size_t)ld); D.h = take(6 * (size_t)ld); D.ps = take(27 * (size_t)ld);
-        D.nd = take(6 * (size_t)ld); D.sc = take(6 * (size_t)ld);
-        D.chi_edges = take((size_t)ld + nl);
-        double* q = loop;
-        auto takel = [&](size_t n) { double* r = q; q += n; return r; };
-        D.le = takel(6 * (size_t)nl); D.len = takel(6 * (size_t)nl); D.lg = takel(6 * (size_t)nl); D.lm = takel(6 * (size_t)nl);
-        D.gam = takel(36 * (size_t)nl); D.nu = takel(6 * (size_t)nl); D.rhs = takel(6 * (size_t)nl);
-    }
-};
-
 // ---- the kernel ---------------------------------------------------------------------------------------------
 template <class T>
 __global__ __launch_bounds__(kPT, 1) void cluster_persist_kernel(typename T::Dev D0, typename T::Dev D1, PersistArgs P)
@@ -1068,6 +958,9 @@ struct PersistKnobs {
         return k;
     }
 };
+// problems the leader's LDS staging cannot hold go to the host-driven solver (the same bound for either pose type)
+inline bool persist_fits(int L, int nl) { return (L + nl + 1 + 255) / 256 <= kLeadMaxBlk; }
+
 template <class T>
 class PersistSolver {
 public:
@@ -1259,11 +1152,8 @@ public:
         if (nl_dense < 0) nl_dense = nl;
         return ensure(L, nl, 2 * ((size_t)T::kD * nl_dense + 1) * ((size_t)T::kD * nl_dense));
     }
-    const Dev& dev() const { return dev_; }
-    bool result_in_second() const { return x_sel_ != 0; }
-    // problems the leader's LDS staging cannot hold go to the host-driven solver
-    static bool fits(int L, int nl) { return (L + nl + 1 + 255) / 256 <= kLeadMaxBlk; }
-    int ld() const { return dev_.ld; }
+    // the optimised poses of the last fetched solve (local indexing 0..hi-lo): the kernel says which of its two views it ended on
+    PoseBlock result() const { return PoseBlock{T::pose_rows(x_sel_ != 0 ? dev_.Xn : dev_.X), dev_.ld}; }
     int workgroups() const { return last_G_; }
 
 private:
@@ -1329,3 +1219,4 @@ private:
 
 }  // namespace ipc
 #include "cluster_literal_band.hpp"   // Levenberg retry of the literal normal equations in the banded layout
+#include "cluster_host.hpp"           // the host-driven solver on the same bindings (Levenberg retry, IPC_CLUSTER_MODE=host, long cells)

@@ -572,248 +572,87 @@ __global__ void gk_quad_bh(ClusterDev D)
 }
 
 // ------------------------------------------------------------------------------------------
-// host driver
+// pose-type binding: what the two host-side solvers (ClusterSolver<T>, cluster_host.hpp: one launch per phase;
+// PersistSolver<T>, cluster_persist.hpp: one persistent launch) need to know about SE(2)
 // ------------------------------------------------------------------------------------------
-class ClusterSolver2 {
-public:
-    ~ClusterSolver2() { if (lband) literal_band_free(lband); }
-    double term_eps = 0.0;             // convergence shortcut of the trial loop (Se2View::term_eps)
-
-    // Solve chain lo..hi (records `chain`) + the loops `members` (indices into the candidate
-    // records; ids in from/to are global vertex ids), starting from the poses `src` (global
-    // indexing).  The optimised poses stay in result() (local indexing 0..hi-lo).
-    // chi_host (optional): per-edge chi2, odometry lo..hi-1 first, then the loops in `members` order.
-    hipError_t solve(hipStream_t st, const double* chain, int estride, const double* cand, int cstride,
-                     const PoseArr& src, int lo, int hi, const std::vector<int>& members, const int* from,
-                     const int* to, int iterations, ClusterOut& out, std::vector<double>* chi_host);
-    const PoseArr& result() const { return dev_.X; }
-
-    // ---- Ops of cluster_dogleg ----
-    hipError_t evaluate_committed(double& chi) { return evaluate(dev_.X, dev_.e, dev_.le, chi); }
-    hipError_t linearize(double& bb, double& bHb, double& hh, double& bh, int& info);
-    hipError_t blend(double alpha, double& c, double& bma);
-    hipError_t trial(double p, double q, double& newChi, bool& anyChanged);
-    void commit() { std::swap(dev_.X, dev_.Xn); std::swap(dev_.e, dev_.en); std::swap(dev_.le, dev_.len); }
-    hipError_t max_edge_chi2(double& mx);
-    hipError_t damped_solve(double lambda, bool& ok, double& hh, double& bh, double& bHh, double& hHh);
-    bool allow_damping = true;          // Levenberg retry of a failed linear solve on the literal normal equations: banded + bordered store
-                                        // (cluster_literal_band.hpp) where the loops form a band, dense up to kMaxDenseN unknowns otherwise
-    static constexpr int kMaxDenseN = 24000;
-    static constexpr int kD = 3;
-    int literal_band_min_n = 3072;      // IPC_LITERAL_BAND_MIN_N: smaller systems keep the dense store (bit for bit as in rounds 3 - 5); < 0: never banded
-    LiteralBand* lband = nullptr; bool lband_stale = true;
-    void want_plain_solve(bool w) { want_plain_ = w; }
-    bool want_plain_ = true;
-    long literal_band_solves() const;
-    const LoopTables& tables() const { return tab_; }
-    hipStream_t stream() const { return st_; }
-    template <class St> void launch_literal_H(const St& S, double lambda)
+struct PersistSe2 {
+    using Dev = ClusterDev;
+    static constexpr int kD = 3, kNPS = 9, kNND = 3, kSC1 = 1, kSC2 = 2;
+    static constexpr int kEdgeDoubles = 43, kLoopDoubles = 27;          // per ld / per loop, + (ld + nl) of chi_edges
+    static constexpr int kPoseRows = 5;                                 // X, Xn: [5][ld], x y th cos sin
+    static constexpr int kLiteralBlock = kGB;                           // threads per block of gk_literal_H
+    // the grid kernels of the host-driven solver
+    static constexpr auto k_eval = &gk_eval;
+    static constexpr auto k_chi_edges = &gk_chi_edges;
+    static constexpr auto k_force = &gk_force;
+    static constexpr auto k_b = &gk_b;
+    static constexpr auto k_bHb_psi = &gk_bHb_psi;
+    static constexpr auto k_assemble = &gk_assemble;
+    static constexpr auto k_nu = &gk_nu;
+    static constexpr auto k_events = &gk_events;
+    static constexpr auto k_rho = &gk_rho;
+    static constexpr auto k_term = &gk_term;
+    static constexpr auto k_h = &gk_h;
+    static constexpr auto k_blend = &gk_blend;
+    static constexpr auto k_update = &gk_update;
+    static constexpr auto k_h_from_dense = &gk_h_from_dense;
+    static constexpr auto k_quad_bh = &gk_quad_bh;
+    template <class St>
+    static void literal_H(dim3 grid, hipStream_t st, const Dev& D, const St& S, double lambda)
     {
-        auto& D = dev_;
-        hipLaunchKernelGGL(gk_literal_H<St>, dim3((D.L + 1 + kGB - 1) / kGB), dim3(kGB), 0, st_, D, S, lambda);
+        hipLaunchKernelGGL(gk_literal_H<St>, grid, dim3(kLiteralBlock), 0, st, D, S, lambda);
     }
-
-private:
-    DevBuf<double> d_H_; size_t capH_ = 0;       // dense system + factor of damped_solve
-    ClusterDev dev_{};
-    hipStream_t st_ = nullptr;
-    int nblk_ = 1;
-    std::vector<double>* chi_host_ = nullptr;
-    int capL_ = 0, capNl_ = 0;
-    DevBuf<double> d_edge_, d_loop_, d_S_, d_partial_, d_scal_;
-    DevBuf<int> d_int_;
-    int* d_info_ = nullptr;             // inside d_scal_
-    PinnedBuf<double> h_scal_;          // pinned [12] + info
-    LoopTables tab_;
-
-    hipError_t ensure(int L, int nl);
-    hipError_t fetch(int n)
+    static double* pose_rows(const PoseArr& X) { return X.x; }          // (rows of one block: carve)
+    __device__ static void load_initial(const Dev& D, const double* src, int V, int i)
     {
-        (void)n;                     // scalars [0, 12) and the solver's info word at [12] travel in one copy
-        IPC_CL_CHK(hipMemcpyAsync(h_scal_, d_scal_, sizeof(double) * 13, hipMemcpyDeviceToHost, st_));
-        return hipStreamSynchronize(st_);
+        const size_t s = (size_t)D.lo + i;
+        auto g = gptr(src);
+        gptr(D.X.x)[i] = g[s]; gptr(D.X.y)[i] = g[(size_t)V + s]; gptr(D.X.th)[i] = g[2 * (size_t)V + s];
+        gptr(D.X.c)[i] = g[3 * (size_t)V + s]; gptr(D.X.s)[i] = g[4 * (size_t)V + s];
     }
-    void sum_partials(int K, int off)
+    __device__ static void eval(const Dev& D, bool trial, int i, double (&v)[1])
     {
-        hipLaunchKernelGGL(gk_sum, dim3(1), dim3(64), 0, st_, (const double*)dev_.partial, nblk_, K, dev_.scal, off);
+        if (trial) gk_eval_at(D, D.Xn, D.en, D.len, i, v); else gk_eval_at(D, D.X, D.e, D.le, i, v);
     }
-    hipError_t evaluate(const PoseArr& Y, double* eo, double* leo, double& chi)
+    __device__ static void chi_edges(const Dev& D, int i) { gk_chi_edges_at(D, i); }
+    __device__ static void force(const Dev& D, int i) { gk_force_at(D, i); }
+    __device__ static void b(const Dev& D, int i, double (&v)[1]) { gk_b_at(D, i, v); }
+    __device__ static void bHb_psi(const Dev& D, int i, double (&v)[1]) { gk_bHb_psi_at(D, i, v); }
+    __device__ static void assemble(const Dev& D, int l1, int l2) { gk_assemble_at(D, l1, l2); }
+    template <class Put, class PutRhs>
+    __device__ static void assemble_core(const Dev& D, int l1, int l2, Put put, PutRhs put_rhs) { gk_assemble_core(D, l1, l2, put, put_rhs); }
+    // the banded kernel's unit of assembly work: the whole 3 x 3 block
+    static constexpr int kAsmRows = 1;
+    template <class Put, class PutRhs>
+    __device__ static void assemble_row(const Dev& D, int l1, int l2, int, Put put, PutRhs put_rhs) { gk_assemble_core(D, l1, l2, put, put_rhs); }
+    __device__ static void nu(const Dev& D, int l) { gk_nu_at(D, l); }
+    __device__ static void events(const Dev& D, int j) { gk_events_at(D, j); }
+    __device__ static void rho(const Dev& D, int i) { gk_rho_at(D, i); }
+    __device__ static void term(const Dev& D, int i) { gk_term_at(D, i); }
+    __device__ static void h(const Dev& D, int i, double (&v)[2]) { gk_h_at(D, i, v); }
+    __device__ static void blend(const Dev& D, double alpha, int i, double (&v)[2]) { gk_blend_at(D, alpha, i, v); }
+    __device__ static void update(const Dev& D, double p, double q, int i, double (&v)[1]) { gk_update_at(D, p, q, i, v); }
+    static void exchange(Dev& D)                 // the view after a commit: committed <-> trial buffers
     {
-        hipLaunchKernelGGL(gk_eval, dim3(nblk_), dim3(kGB), 0, st_, dev_, Y, eo, leo);
-        sum_partials(1, 7);
-        IPC_CL_CHK(fetch(8));
-        chi = h_scal_[7];
-        return hipSuccess;
+        PoseArr tx = D.X; D.X = D.Xn; D.Xn = tx;
+        double* t = D.e; D.e = D.en; D.en = t;
+        t = D.le; D.le = D.len; D.len = t;
     }
-};
-
-inline hipError_t ClusterSolver2::ensure(int L, int nl)
-{
-    if (!d_scal_) {                                  // (the last thing the block creates: a failure part way runs it again)
-        IPC_CL_CHK(h_scal_.alloc(16));
-        IPC_CL_CHK(d_scal_.alloc(16));
-        d_info_ = reinterpret_cast<int*>(d_scal_ + 12);
-    }
-    if (L > capL_ || nl > capNl_) {
-        const int nL = std::max(L, capL_), nN = std::max(nl, capNl_);
-        capL_ = capNl_ = 0;
-        const size_t ld = (size_t)nL + 2;
-        IPC_CL_CHK(d_edge_.alloc(43 * ld + ld + nN));
-        IPC_CL_CHK(d_loop_.alloc(27 * (size_t)nN + 8));
-        IPC_CL_CHK(d_S_.alloc(2 * (3 * (size_t)nN + 1) * (3 * (size_t)nN)));   // system + factor
-        IPC_CL_CHK(d_partial_.alloc(4 * ((nL + nN + 1 + kGB) / kGB + 1)));
-        IPC_CL_CHK(d_int_.alloc(LoopTables::capacity(nL, nN)));
-        capL_ = nL; capNl_ = nN;
-    }
-    return hipSuccess;
-}
-
-inline hipError_t ClusterSolver2::linearize(double& bb, double& bHb, double& hh, double& bh, int& info)
-{
-    ClusterDev& D = dev_;
-    const dim3 grid(nblk_), block(kGB);
-    const int L = D.L, nl = D.nl, ld = D.ld;
-    hipLaunchKernelGGL(gk_force, grid, block, 0, st_, D);
-    hipLaunchKernelGGL(gk_b, grid, block, 0, st_, D);
-    sum_partials(1, 0);
-    hipLaunchKernelGGL(gk_bHb_psi, grid, block, 0, st_, D);
-    sum_partials(1, 1);
-    if (!want_plain_) {                              // cluster_dogleg: only b, b^T b and b^T H b are needed, a damped solve follows
-        IPC_CL_CHK(hipGetLastError());
-        IPC_CL_CHK(fetch(4));
-        bb = h_scal_[0]; bHb = h_scal_[1]; hh = 0.0; bh = 0.0; info = 1;
-        return hipSuccess;
-    }
-    hipLaunchKernelGGL(gk_scan, dim3(9), dim3(1024), 0, st_, D.ps, 9, L, ld);
-    hipLaunchKernelGGL(gk_assemble, dim3((nl + 63) / 64, nl), dim3(64), 0, st_, D);
-    IPC_CL_CHK(chol_solve_device(D.S, D.S + (size_t)(3 * nl + 1) * (3 * nl), 3 * nl, D.rhs, d_info_, st_));
-    hipLaunchKernelGGL(gk_nu, dim3((nl + 63) / 64), dim3(64), 0, st_, D);
-    hipLaunchKernelGGL(gk_events, dim3((L + 2 + kGB - 1) / kGB), block, 0, st_, D);
-    hipLaunchKernelGGL(gk_scan, dim3(3), dim3(1024), 0, st_, D.nd, 3, L, ld);
-    hipLaunchKernelGGL(gk_rho, grid, block, 0, st_, D);
-    hipLaunchKernelGGL(gk_scan, dim3(1), dim3(1024), 0, st_, D.sc, 1, L, ld);
-    hipLaunchKernelGGL(gk_term, grid, block, 0, st_, D);
-    hipLaunchKernelGGL(gk_scan, dim3(2), dim3(1024), 0, st_, D.sc + ld, 2, L, ld);
-    hipLaunchKernelGGL(gk_h, grid, block, 0, st_, D);
-    sum_partials(2, 2);
-    IPC_CL_CHK(hipGetLastError());
-    IPC_CL_CHK(fetch(4));
-    std::memcpy(&info, h_scal_ + 12, sizeof(int));
-    bb = h_scal_[0]; bHb = h_scal_[1]; hh = h_scal_[2]; bh = h_scal_[3];
-    return hipSuccess;
-}
-
-inline hipError_t ClusterSolver2::damped_solve(double lambda, bool& ok, double& hh, double& bh, double& bHh, double& hHh)
-{
-    ClusterDev& D = dev_;
-    const int n = 3 * D.L;
-    ok = false;
-    IPC_CL_CHK(hipMemsetAsync(d_info_, 0, sizeof(int), st_));
-    bool banded = false;
-    if (literal_band_min_n >= 0 && n >= literal_band_min_n)
-        IPC_CL_CHK(literal_band_damped(*this, lambda, banded, D.sc, d_info_));   // (solution in the scan workspace: 3 ld doubles)
-    if (!banded) {
-        if (n > kMaxDenseN) return hipSuccess;                   // (no band and too large for the dense store: the solve reports Fail)
-        const size_t m = (size_t)(n + 1) * n;
-        if (2 * m > capH_) {
-            capH_ = 0;
-            IPC_CL_CHK(d_H_.alloc(2 * m));
-            capH_ = 2 * m;
-        }
-        IPC_CL_CHK(hipMemsetAsync(d_H_, 0, sizeof(double) * m, st_));
-        hipLaunchKernelGGL(gk_literal_H<DenseStore>, dim3((D.L + 1 + kGB - 1) / kGB), dim3(kGB), 0, st_, D, DenseStore{d_H_, n, 3}, lambda);
-        IPC_CL_CHK(chol_solve_device(d_H_, d_H_ + m, n, D.sc, d_info_, st_));
-    }
-    hipLaunchKernelGGL(gk_h_from_dense, dim3(nblk_), dim3(kGB), 0, st_, D, (const double*)D.sc);
-    sum_partials(2, 2);
-    hipLaunchKernelGGL(gk_quad_bh, dim3(nblk_), dim3(kGB), 0, st_, D);
-    sum_partials(2, 4);
-    IPC_CL_CHK(hipGetLastError());
-    IPC_CL_CHK(fetch(6));
-    int info;
-    std::memcpy(&info, h_scal_ + 12, sizeof(int));
-    hh = h_scal_[2]; bh = h_scal_[3]; bHh = h_scal_[4]; hHh = h_scal_[5];
-    ok = info == 0 && hh == hh;
-    IPC_CL_CHK(hipMemsetAsync(d_info_, 0, sizeof(int), st_));
-    return hipSuccess;
-}
-
-inline hipError_t ClusterSolver2::blend(double alpha, double& c, double& bma)
-{
-    hipLaunchKernelGGL(gk_blend, dim3(nblk_), dim3(kGB), 0, st_, dev_, alpha);
-    sum_partials(2, 4);
-    IPC_CL_CHK(fetch(6));
-    c = h_scal_[4]; bma = h_scal_[5];
-    return hipSuccess;
-}
-
-inline hipError_t ClusterSolver2::trial(double p, double q, double& newChi, bool& anyChanged)
-{
-    hipLaunchKernelGGL(gk_update, dim3(nblk_), dim3(kGB), 0, st_, dev_, p, q);
-    sum_partials(1, 6);
-    IPC_CL_CHK(evaluate(dev_.Xn, dev_.en, dev_.len, newChi));
-    anyChanged = h_scal_[6] != 0.0;
-    return hipSuccess;
-}
-
-inline hipError_t ClusterSolver2::max_edge_chi2(double& mx_out)
-{
-    ClusterDev& D = dev_;
-    hipLaunchKernelGGL(gk_chi_edges, dim3(nblk_), dim3(kGB), 0, st_, D);
-    IPC_CL_CHK(hipGetLastError());
-    std::vector<double> local;
-    std::vector<double>& chi = chi_host_ ? *chi_host_ : local;
-    chi.resize((size_t)D.L + D.nl);
-    IPC_CL_CHK(hipMemcpyAsync(chi.data(), D.chi_edges, sizeof(double) * chi.size(), hipMemcpyDeviceToHost, st_));
-    IPC_CL_CHK(hipStreamSynchronize(st_));
-    double mx = 0.0;
-    bool nan = false;
-    for (double c : chi) { if (c != c) nan = true; else mx = std::max(mx, c); }
-    mx_out = (nan && !(mx > 0.0)) ? std::nan("") : mx;      // (max over the edges that have a number: se2_cell.hpp)
-    return hipSuccess;
-}
-
-inline hipError_t ClusterSolver2::solve(hipStream_t st, const double* chain, int estride, const double* cand,
-                                        int cstride, const PoseArr& src, int lo, int hi,
-                                        const std::vector<int>& members, const int* from, const int* to,
-                                        int iterations, ClusterOut& out, std::vector<double>* chi_host)
-{
-    const int L = hi - lo, nl = (int)members.size(), NS = 3 * nl;
-    IPC_CL_CHK(ensure(L, nl));
-    const int ld = L + 2;
-    st_ = st; chi_host_ = chi_host;
-    ClusterDev& D = dev_;
-    D.chain = chain; D.estride = estride; D.lo = lo; D.L = L; D.nl = nl; D.ld = ld;
-    D.cand = cand; D.cstride = cstride;
-    {   // carve the workspaces
-        double* p = d_edge_;
+    static void carve(Dev& D, double* edge, double* loop, int ld, int nl)
+    {
+        double* p = edge;
         auto take = [&](size_t n) { double* q = p; p += n; return q; };
         D.X = PoseArr{take(ld), take(ld), take(ld), take(ld), take(ld)};
         D.Xn = PoseArr{take(ld), take(ld), take(ld), take(ld), take(ld)};
-        D.e = take(3 * ld); D.en = take(3 * ld); D.g = take(3 * ld); D.m = take(3 * ld);
-        D.b = take(3 * ld); D.h = take(3 * ld); D.ps = take(9 * ld); D.nd = take(3 * ld); D.sc = take(3 * ld);
-        D.chi_edges = take(ld + nl);
-        double* q = d_loop_;
+        D.e = take(3 * (size_t)ld); D.en = take(3 * (size_t)ld); D.g = take(3 * (size_t)ld); D.m = take(3 * (size_t)ld);
+        D.b = take(3 * (size_t)ld); D.h = take(3 * (size_t)ld); D.ps = take(9 * (size_t)ld); D.nd = take(3 * (size_t)ld);
+        D.sc = take(3 * (size_t)ld);
+        D.chi_edges = take((size_t)ld + nl);
+        double* q = loop;
         auto takel = [&](size_t n) { double* r = q; q += n; return r; };
-        D.le = takel(3 * nl); D.len = takel(3 * nl); D.lg = takel(3 * nl); D.lm = takel(3 * nl);
-        D.gam = takel(9 * nl); D.nu = takel(3 * nl); D.rhs = takel(3 * nl);
-        D.S = d_S_; D.ldS = NS + 1;
-        D.partial = d_partial_; D.scal = d_scal_;
+        D.le = takel(3 * (size_t)nl); D.len = takel(3 * (size_t)nl); D.lg = takel(3 * (size_t)nl); D.lm = takel(3 * (size_t)nl);
+        D.gam = takel(9 * (size_t)nl); D.nu = takel(3 * (size_t)nl); D.rhs = takel(3 * (size_t)nl);
     }
-    tab_.build(lo, hi, members, from, to);
-    lband_stale = true;
-    IPC_CL_CHK(hipMemcpyAsync(d_int_, tab_.host.data(), sizeof(int) * tab_.size(), hipMemcpyHostToDevice, st));
-    IPC_CL_CHK(hipStreamSynchronize(st));           // the host table is pageable and reused
-    D.lfrom = tab_.lfrom(d_int_); D.lto = tab_.lto(d_int_); D.lcand = tab_.lcand(d_int_);
-    D.adj_ptr = tab_.adj_ptr(d_int_); D.adj_item = tab_.adj_item(d_int_);
-    D.ev_ptr = tab_.ev_ptr(d_int_); D.ev_item = tab_.ev_item(d_int_);
-    const double* sp[5] = {src.x, src.y, src.th, src.c, src.s};
-    double* xp[5] = {D.X.x, D.X.y, D.X.th, D.X.c, D.X.s};
-    for (int k = 0; k < 5; ++k)
-        IPC_CL_CHK(hipMemcpyAsync(xp[k], sp[k] + lo, sizeof(double) * (L + 1), hipMemcpyDeviceToDevice, st));
-    nblk_ = (L + nl + 1 + kGB - 1) / kGB;            // indices 0 .. L+nl
-    IPC_CL_CHK(hipMemsetAsync(d_info_, 0, sizeof(int), st));
-    return cluster_dogleg(*this, iterations, out, term_eps, tab_.L + tab_.nl, allow_damping);
-}
+};
 
 }  // namespace ipc

@@ -827,8 +827,8 @@ struct ipc_engine {
     double* d_open = nullptr;                          // [5][vcap] open-loop x y th cos sin: d_open_own, or d_pose0 itself (SE3)
     DevBuf<double> d_open_own;
     DevBuf<double> d_cur;                              // [5][vcap] current estimates + kPoseTrail doubles (the tail transform, k_apply_accept)
-    std::unique_ptr<ClusterSolver2> cluster;
-    std::unique_ptr<ClusterSolver3> cluster3;                // SE3: d_open is d_pose0 itself, d_cur is [12][V]
+    std::unique_ptr<ClusterSolver<PersistSe2>> cluster;
+    std::unique_ptr<ClusterSolver<PersistSe3>> cluster3;     // SE3: d_open is d_pose0 itself, d_cur is [12][V]
     // device-resident dog-leg (cluster_persist.hpp): the default; IPC_CLUSTER_MODE=host keeps the host-driven kernels
     bool persist = true;
     bool last_persist = false;                         // which solver holds the poses of the last cluster solve
@@ -1538,18 +1538,23 @@ static Se3View make_view3(const ipc_engine* h)
 }
 
 static int ensure_incremental(ipc_engine* h, const char* who);
-static PoseArr pose_arr(double* base, int V);
+
+// An engine has the solvers of its own pose type only (dim 2: cluster / persist2 / s2, dim 3: cluster3 / persist3 / s3):
+// the same call on whichever exists goes through these, f being a generic lambda.
+template <class F> static auto with_host(const ipc_engine* h, F f) { return h->dim == 3 ? f(*h->cluster3) : f(*h->cluster); }
+template <class F> static auto with_persist(const ipc_engine* h, F f) { return h->dim == 3 ? f(*h->persist3) : f(*h->persist2); }
+template <class F> static auto with_persist(const ipc_engine* h, const ipc_engine::SpecSlot& sl, F f) { return h->dim == 3 ? f(*sl.s3) : f(*sl.s2); }
 
 // One cluster solve (chain lo..hi of the records `chain` + the loops `members`, from the poses `src`: SE2 [5][V],
 // SE3 [12][V]) on the engine's stream, by the device-resident dog-leg or (IPC_CLUSTER_MODE=host) the host-driven one.
-// Blocks until the result record is back; the optimised poses stay in the solver (cluster_result2 / cluster_result3).
+// Blocks until the result record is back; the optimised poses stay in the solver (cluster_result).
 static hipError_t cluster_solve(ipc_engine* h, const double* chain, double* src, int lo, int hi, const std::vector<int>& members,
                                 int iters, ClusterOut& o, bool force_host = false)
 {
     // (nothing of the candidate pipeline may share the GPU with this launch: its workgroups and the pipeline's together
     // could exceed the CUs, and workgroups that wait at grid barriers must all be resident)
     if (!h->slots.empty() && h->spec_head >= 0) { if (int rc = spec_quiesce(h, true)) return hipErrorUnknown; }
-    h->last_persist = !force_host && h->persist && PersistSolver<PersistSe2>::fits(hi - lo, (int)members.size());
+    h->last_persist = !force_host && h->persist && persist_fits(hi - lo, (int)members.size());
     if (h->last_persist) {
         // A LOST launch (a grid barrier timed out: some workgroup of the launch never became resident, e.g. beside a foreign
         // tenant's kernels) says nothing about the problem: the same launch is tried again -- the pipeline is quiesced here, so it
@@ -1557,17 +1562,13 @@ static hipError_t cluster_solve(ipc_engine* h, const double* chain, double* src,
         // co-residency, one launch per phase) take over.  Round 5 went straight to them.
         bool lost = false;
         for (int attempt = 0; attempt < 3; ++attempt) {
-            if (h->dim == 3) {
-                IPC_CL_CHK(h->persist3->launch(h->own_stream, chain, h->estride, h->d_cand, h->cstride, src, h->vcap, lo, hi, members,
-                                               h->h_from.data(), h->h_to.data(), iters));
-                IPC_CL_CHK(h->persist3->wait(o));
-                lost = h->persist3->timed_out();
-            } else {
-                IPC_CL_CHK(h->persist2->launch(h->own_stream, chain, h->estride, h->d_cand, h->cstride, src, h->vcap, lo, hi, members,
-                                               h->h_from.data(), h->h_to.data(), iters));
-                IPC_CL_CHK(h->persist2->wait(o));
-                lost = h->persist2->timed_out();
-            }
+            IPC_CL_CHK(with_persist(h, [&](auto& s) {
+                IPC_CL_CHK(s.launch(h->own_stream, chain, h->estride, h->d_cand, h->cstride, src, h->vcap, lo, hi, members,
+                                    h->h_from.data(), h->h_to.data(), iters));
+                IPC_CL_CHK(s.wait(o));
+                lost = s.timed_out();
+                return hipSuccess;
+            }));
             if (!lost) break;
             ++h->persist_timeouts;
             if (attempt < 2) ++h->persist_relaunches;
@@ -1579,22 +1580,16 @@ static hipError_t cluster_solve(ipc_engine* h, const double* chain, double* src,
         h->last_persist = false;
         ++h->lm_fallbacks;
     }
-    if (h->dim == 3)
-        return h->cluster3->solve(h->own_stream, chain, h->estride, h->d_cand, h->cstride, src, h->vcap, lo, hi, members,
-                                  h->h_from.data(), h->h_to.data(), iters, o, nullptr);
-    return h->cluster->solve(h->own_stream, chain, h->estride, h->d_cand, h->cstride, pose_arr(src, h->vcap), lo, hi, members,
-                             h->h_from.data(), h->h_to.data(), iters, o, nullptr);
+    return with_host(h, [&](auto& s) {
+        return s.solve(h->own_stream, chain, h->estride, h->d_cand, h->cstride, src, h->vcap, lo, hi, members,
+                       h->h_from.data(), h->h_to.data(), iters, o, nullptr);
+    });
 }
-static PoseArr cluster_result2(const ipc_engine* h)
+// the optimised poses of the last cluster_solve, in whichever solver ran it
+static PoseBlock cluster_result(const ipc_engine* h)
 {
-    if (!h->last_persist) return h->cluster->result();
-    return h->persist2->result_in_second() ? h->persist2->dev().Xn : h->persist2->dev().X;
-}
-static const double* cluster_result3(const ipc_engine* h, int& ld)
-{
-    if (!h->last_persist) { ld = h->cluster3->ld(); return h->cluster3->result(); }
-    ld = h->persist3->ld();
-    return h->persist3->result_in_second() ? h->persist3->dev().Xn : h->persist3->dev().X;
+    const auto result = [](auto& s) { return s.result(); };
+    return h->last_persist ? with_persist(h, result) : with_host(h, result);
 }
 
 // Cells beyond the capacity of every cell kernel (SE3 > 4096 poses, SE2 > 16384 with the default
@@ -1782,10 +1777,8 @@ static int host_cell_solve(ipc_engine* h, int2 cell, bool damped, bool literal, 
     }
     const double te = h->term_eps;
     auto set_eps = [&](double v) {
-        if (h->cluster) h->cluster->term_eps = v;
-        if (h->cluster3) h->cluster3->term_eps = v;
-        if (h->persist2) h->persist2->term_eps = v;
-        if (h->persist3) h->persist3->term_eps = v;
+        with_host(h, [&](auto& s) { s.term_eps = v; });      // (both exist: the callers went through ensure_incremental, as cluster_solve needs)
+        with_persist(h, [&](auto& s) { s.term_eps = v; });
     };
     if (literal) set_eps(0.0);
     const hipError_t e = cluster_solve(h, h->d_chain, h->d_open, lo, hi, members, iters, o);
@@ -3313,9 +3306,18 @@ __global__ void k_append_state_tail(int V0, int n, const double* open, int vs, S
     else se3_tail_apply(D, open, Vs, dst, i);
 }
 
-static PoseArr pose_arr(double* base, int V)
+// the engine's two one-at-a-time solvers of pose type T, with the engine's knobs
+template <class T>
+static void make_solvers(ipc_engine* h, std::unique_ptr<ClusterSolver<T>>& host, std::unique_ptr<PersistSolver<T>>& persist)
 {
-    return PoseArr{base, base + (size_t)V, base + 2 * (size_t)V, base + 3 * (size_t)V, base + 4 * (size_t)V};
+    if (!host) {
+        host.reset(new ClusterSolver<T>()); host->term_eps = h->term_eps; host->allow_damping = h->lm_retry;
+        host->literal_band_min_n = h->literal_band_min_n;
+    }
+    if (!persist) {
+        persist.reset(new PersistSolver<T>(h->knobs)); persist->term_eps = h->term_eps; persist->d_prof = h->d_prof;
+        if (h->max_helpers >= 0) persist->max_helpers = h->max_helpers;
+    }
 }
 
 static int ensure_incremental(ipc_engine* h, const char* who)
@@ -3328,14 +3330,7 @@ static int ensure_incremental(ipc_engine* h, const char* who)
             HIPCHK(h->d_cur.alloc(12 * (size_t)h->vcap + kPoseTrail));
             if (int rc = reset_current(h)) return rc;
         }
-        if (!h->cluster3) {
-            h->cluster3.reset(new ClusterSolver3()); h->cluster3->term_eps = h->term_eps; h->cluster3->allow_damping = h->lm_retry;
-            h->cluster3->literal_band_min_n = h->literal_band_min_n;
-        }
-        if (!h->persist3) {
-            h->persist3.reset(new PersistSolver<PersistSe3>(h->knobs)); h->persist3->term_eps = h->term_eps; h->persist3->d_prof = h->d_prof;
-            if (h->max_helpers >= 0) h->persist3->max_helpers = h->max_helpers;
-        }
+        make_solvers(h, h->cluster3, h->persist3);
         return IPC_OK;
     }
     if (!h->d_cur) {
@@ -3346,14 +3341,7 @@ static int ensure_incremental(ipc_engine* h, const char* who)
         HIPCHK(hipGetLastError());
         if (int rc = reset_current(h)) return rc;
     }
-    if (!h->cluster) {
-        h->cluster.reset(new ClusterSolver2()); h->cluster->term_eps = h->term_eps; h->cluster->allow_damping = h->lm_retry;
-        h->cluster->literal_band_min_n = h->literal_band_min_n;
-    }
-    if (!h->persist2) {
-        h->persist2.reset(new PersistSolver<PersistSe2>(h->knobs)); h->persist2->term_eps = h->term_eps; h->persist2->d_prof = h->d_prof;
-        if (h->max_helpers >= 0) h->persist2->max_helpers = h->max_helpers;
-    }
+    make_solvers(h, h->cluster, h->persist2);
     return IPC_OK;
 }
 
@@ -3527,23 +3515,19 @@ static ClusterSpec cluster_of(const ipc_engine* h, int k) { return cluster_of(h,
 
 // IPC::agreementCheck's accept branch (src/consensus.cpp:69-71) on the pose buffer `dst` ([5 | 12][V]): the optimised window
 // replaces the poses, the tail is re-propagated (propagateCurrentGuess, consensus_utils.cpp:61-71).  Enqueued on `st`.
-static int apply_accept(ipc_engine* h, hipStream_t st, double* dst, const double* parent, int lo, int hi, const PoseArr* X2,
-                        const double* X3, int ld3)
+static int apply_accept(ipc_engine* h, hipStream_t st, double* dst, const double* parent, int lo, int hi, PoseBlock X)
 {
     if (h->dim == 3)
-        hipLaunchKernelGGL(k_apply_accept<12>, dim3(1), dim3(256), 0, st, h->V, h->vcap, lo, hi, parent, X3, ld3, (const double*)h->d_open, dst);
-    else if (X2->th - X2->y != X2->y - X2->x || X2->c - X2->th != X2->y - X2->x || X2->s - X2->c != X2->y - X2->x)
-        return fail(IPC_ERR_STATE, "apply_accept: the solver's pose arrays are not rows of one block");
-    else                                            // (x, y, th, c, s: rows of one block, ClusterSolver2 / PersistSe2::carve)
-        hipLaunchKernelGGL(k_apply_accept<5>, dim3(1), dim3(256), 0, st, h->V, h->vcap, lo, hi, parent, X2->x, (int)(X2->y - X2->x),
-                           (const double*)h->d_open, dst);
+        hipLaunchKernelGGL(k_apply_accept<12>, dim3(1), dim3(256), 0, st, h->V, h->vcap, lo, hi, parent, (const double*)X.p, X.ld, (const double*)h->d_open, dst);
+    else
+        hipLaunchKernelGGL(k_apply_accept<5>, dim3(1), dim3(256), 0, st, h->V, h->vcap, lo, hi, parent, (const double*)X.p, X.ld, (const double*)h->d_open, dst);
     HIPCHK(hipGetLastError());
     return IPC_OK;
 }
 // ... on the current poses; k joins the set.
-static int commit_accept(ipc_engine* h, hipStream_t st, int k, int lo, int hi, const PoseArr* X2, const double* X3, int ld3)
+static int commit_accept(ipc_engine* h, hipStream_t st, int k, int lo, int hi, PoseBlock X)
 {
-    if (int rc = apply_accept(h, st, h->d_cur, h->d_cur, lo, hi, X2, X3, ld3)) return rc;
+    if (int rc = apply_accept(h, st, h->d_cur, h->d_cur, lo, hi, X)) return rc;
     if (std::find(h->cns.begin(), h->cns.end(), k) != h->cns.end()) h->cns_dups = true;
     h->cns.push_back(k);
     return IPC_OK;
@@ -3574,6 +3558,15 @@ static int probe_stream_concurrency(hipStream_t* st, int n)
     return std::max(1, std::min(n, (int)std::lround(n * 1e-3 / std::max(wall - 0.1e-3, 1e-3))));
 }
 
+// the persistent solver of pipeline slot q
+template <class T>
+static hipError_t make_slot_solver(ipc_engine* h, int q, std::unique_ptr<PersistSolver<T>>& s)
+{
+    s.reset(new PersistSolver<T>(h->knobs)); s->term_eps = h->term_eps; s->d_prof = q == 0 ? h->d_prof : nullptr;
+    s->d_abort_word = h->d_abort + q;
+    return s->reserve(h->vcap - 1, std::max(256, std::min(h->N + 1, 16384)), 256);
+}
+
 static int spec_ensure(ipc_engine* h)
 {
     if (!h->slots.empty()) return IPC_OK;
@@ -3590,15 +3583,7 @@ static int spec_ensure(ipc_engine* h)
         ipc_engine::SpecSlot& sl = h->slots[q];
         HIPCHK(pipeline_stream(h->device, q, &sl.st));
         HIPCHK(sl.done.create(hipEventDisableTiming));
-        if (h->dim == 3) {
-            sl.s3.reset(new PersistSolver<PersistSe3>(h->knobs)); sl.s3->term_eps = h->term_eps; sl.s3->d_prof = q == 0 ? h->d_prof : nullptr;
-            sl.s3->d_abort_word = h->d_abort + q;
-            HIPCHK(sl.s3->reserve(h->vcap - 1, std::max(256, std::min(h->N + 1, 16384)), 256));
-        } else {
-            sl.s2.reset(new PersistSolver<PersistSe2>(h->knobs)); sl.s2->term_eps = h->term_eps; sl.s2->d_prof = q == 0 ? h->d_prof : nullptr;
-            sl.s2->d_abort_word = h->d_abort + q;
-            HIPCHK(sl.s2->reserve(h->vcap - 1, std::max(256, std::min(h->N + 1, 16384)), 256));
-        }
+        HIPCHK(h->dim == 3 ? make_slot_solver(h, q, sl.s3) : make_slot_solver(h, q, sl.s2));
     }
     if (!h->window_forced) {
         hipStream_t sts[64];
@@ -3767,21 +3752,15 @@ static int spec_launch(ipc_engine* h, int q, int p, int helpers, bool expect_rej
         const int n = (h->dim == 2 ? 3 : 6) * (int)c.members.size(), nt = (n + 63) / 64, wanted = (nt * (nt + 1) / 2 + kPSG - 1) / kPSG;
         helpers = std::min(helpers, std::max(h->helper_limit_reject, (int)(0.45 * wanted)));
     }
-    if (h->dim == 3) sl.s3->max_helpers = helpers; else sl.s2->max_helpers = helpers;
-    if (h->dim == 3) sl.s3->economy = expect_reject; else sl.s2->economy = expect_reject;
-    if (h->dim == 3) {
-        sl.s3->launch_id = sl.launch_id;
-        HIPCHK(sl.s3->launch(sl.st, h->d_chain, h->estride, h->d_cand, h->cstride, S.d_poses, h->vcap, c.lo, c.hi, c.members,
-                             h->h_from.data(), h->h_to.data(), c.iters));
-    } else {
-        sl.s2->launch_id = sl.launch_id;
-        HIPCHK(sl.s2->launch(sl.st, h->d_chain, h->estride, h->d_cand, h->cstride, S.d_poses, h->vcap, c.lo, c.hi, c.members,
-                             h->h_from.data(), h->h_to.data(), c.iters));
-    }
+    HIPCHK(with_persist(h, sl, [&](auto& s) {
+        s.max_helpers = helpers; s.economy = expect_reject; s.launch_id = sl.launch_id;
+        return s.launch(sl.st, h->d_chain, h->estride, h->d_cand, h->cstride, S.d_poses, h->vcap, c.lo, c.hi, c.members,
+                        h->h_from.data(), h->h_to.data(), c.iters);
+    }));
     HIPCHK(hipEventRecord(sl.done, sl.st));
     sl.t_launch = std::chrono::steady_clock::now();
     // (a kernel this slot was told to give up may still be running in front of the new one, never beside it)
-    sl.busy_wgs = std::max(sl.busy_wgs, h->dim == 3 ? sl.s3->workgroups() : sl.s2->workgroups());
+    sl.busy_wgs = std::max(sl.busy_wgs, with_persist(h, sl, [](auto& s) { return s.workgroups(); }));
     return IPC_OK;
 }
 
@@ -3800,13 +3779,7 @@ static int spec_make_tentative(ipc_engine* h, int p, int q)
     if (P.has_ready) HIPCHK(hipStreamWaitEvent(sl.st, P.ready, 0));
     else if (!P.owned && h->commit_count) HIPCHK(hipStreamWaitEvent(sl.st, h->ev_commit, 0));
     if (h->cand_event) HIPCHK(hipStreamWaitEvent(sl.st, h->ev_cand, 0));  // (open-loop poses ipc_append_odometry wrote on own_stream since the solve was launched: the tail reads them)
-    if (h->dim == 3) {
-        const double* res = sl.s3->result_in_second() ? sl.s3->dev().Xn : sl.s3->dev().X;
-        if (int rc = apply_accept(h, sl.st, T.d_poses, P.d_poses, R.lo, R.hi, nullptr, res, sl.s3->ld())) return rc;
-    } else {
-        const PoseArr X = sl.s2->result_in_second() ? sl.s2->dev().Xn : sl.s2->dev().X;
-        if (int rc = apply_accept(h, sl.st, T.d_poses, P.d_poses, R.lo, R.hi, &X, nullptr, 0)) return rc;
-    }
+    if (int rc = apply_accept(h, sl.st, T.d_poses, P.d_poses, R.lo, R.hi, with_persist(h, sl, [](auto& s) { return s.result(); }))) return rc;
     HIPCHK(hipEventRecord(T.ready, sl.st));
     T.has_ready = true;
     // (on a stream of its own: the next solve on the new state often lands on this very slot's stream, and the prediction
@@ -3917,9 +3890,13 @@ static int spec_pump(ipc_engine* h)
         sl.busy_wgs = 0;
         if (sl.cand < 0) continue;                                            // (a solve that was told to give up has left the GPU)
         ClusterOut o;
-        HIPCHK(h->dim == 3 ? sl.s3->fetch(o) : sl.s2->fetch(o));
-        const bool aborted = h->dim == 3 ? sl.s3->aborted() : sl.s2->aborted();
-        const bool lost = h->dim == 3 ? sl.s3->timed_out() : sl.s2->timed_out();
+        bool aborted = false, lost = false;
+        double device_us = 0.0;
+        HIPCHK(with_persist(h, sl, [&](auto& s) {
+            const hipError_t e = s.fetch(o);
+            aborted = s.aborted(); lost = s.timed_out(); device_us = s.device_us();
+            return e;
+        }));
         const int p = sl.pos;
         --h->spec_states[sl.state].users;
         const bool stale = aborted || p < h->spec_head || sl.state != spec_state_at(h, p);
@@ -3927,7 +3904,7 @@ static int spec_pump(ipc_engine* h)
             const auto us = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::micro>(t - h->spec_log_t0).count(); };
             fprintf(h->spec_log, "solve,%.0f,%.0f,%d,%d,%d,%d,%d,%d,%d,%d,%.0f,%.4g\n", us(sl.t_launch), us(std::chrono::steady_clock::now()), p, sl.cand, sl.expect,
                     h->spec_states[sl.state].pos, stale ? (aborted ? 2 : 1) : 0, !(o.max_chi2 > sl.th) ? 1 : 0, o.iterations, sl.nclu,
-                    h->dim == 3 ? sl.s3->device_us() : sl.s2->device_us(), sl.pred_ratio);
+                    device_us, sl.pred_ratio);
         }
         sl.cand = -1;
         if (stale) { ++h->spec_wasted; continue; }
@@ -3940,7 +3917,7 @@ static int spec_pump(ipc_engine* h)
         ++h->pred_conf[sl.expect + 1][R.agree ? 1 : 0];
         {
             const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - sl.t_launch).count();
-            const double dev = 1e-6 * (h->dim == 3 ? sl.s3->device_us() : sl.s2->device_us());
+            const double dev = 1e-6 * device_us;
             if (R.agree) { h->st_acc_s += dt; h->st_acc_dev_s += dev; h->st_acc_it += o.iterations; ++h->st_acc_n; }
             else { h->st_rej_s += dt; h->st_rej_dev_s += dev; h->st_rej_it += o.iterations; ++h->st_rej_n; }
         }
@@ -4060,7 +4037,7 @@ static int spec_pump(ipc_engine* h)
         const int helpers = std::min(std::min(h->helper_limit, gmax - 1), h->n_cu - 8 - busy - 1);
         if (helpers < std::min(8, h->helper_limit) && running > 0) { why = 2; break; }        // (wait for a solve to leave)
         const int tip = spec_state_at(h, lp);
-        if (!PersistSolver<PersistSe2>::fits(h->V, (int)h->spec_states[tip].cns.size() + 1)) { why = 3; break; }
+        if (!persist_fits(h->V, (int)h->spec_states[tip].cns.size() + 1)) { why = 3; break; }
         if (int rc = spec_launch(h, q, lp, std::max(0, helpers), expect_reject, (cur_pred || file_pred) ? (pa ? 1 : 0) : -1,
                                   cur_pred && cand_lp < cur_n ? cur_pred[cand_lp] / h->prm.slow_reject_th : -1.0)) return rc;
         if (gated) behind += !tied;
@@ -4142,14 +4119,7 @@ static int agreement_check_speculative(ipc_engine* h, int k, int* agrees, ipc_ch
         HIPCHK(cluster_solve(h, h->d_chain, h->d_cur, c.lo, c.hi, c.members, c.iters, o));
         agree = !(o.max_chi2 > th);
         if (agree) {
-            int rld = 0;
-            if (h->dim == 3) {
-                const double* res = cluster_result3(h, rld);
-                if (int rc = commit_accept(h, h->own_stream, k, R.lo, R.hi, nullptr, res, rld)) return rc;
-            } else {
-                const PoseArr X = cluster_result2(h);
-                if (int rc = commit_accept(h, h->own_stream, k, R.lo, R.hi, &X, nullptr, 0)) return rc;
-            }
+            if (int rc = commit_accept(h, h->own_stream, k, R.lo, R.hi, cluster_result(h))) return rc;
             HIPCHK(hipEventRecord(h->ev_commit, h->own_stream));
             ++h->commit_count;
         }
@@ -4198,7 +4168,7 @@ extern "C" int ipc_agreement_check(ipc_engine_t* h, int k, int* agrees, ipc_chec
     if (h->N == 0) return fail(IPC_ERR_STATE, "ipc_agreement_check: no candidates set");
     if (k < 0 || k >= h->N) return fail(IPC_ERR_ARG, "ipc_agreement_check: candidate %d of %d", k, h->N);
     if (int rc = ensure_incremental(h, "ipc_agreement_check")) return rc;
-    if (h->persist && h->spec_window > 1 && PersistSolver<PersistSe2>::fits(h->V, (int)h->cns.size() + 1))
+    if (h->persist && h->spec_window > 1 && persist_fits(h->V, (int)h->cns.size() + 1))
         return agreement_check_speculative(h, k, agrees, info);
     if (int rc = spec_quiesce(h, true)) return rc;
     const ClusterSpec c = cluster_of(h, k);
@@ -4206,14 +4176,7 @@ extern "C" int ipc_agreement_check(ipc_engine_t* h, int k, int* agrees, ipc_chec
     HIPCHK(cluster_solve(h, h->d_chain, h->d_cur, c.lo, c.hi, c.members, c.iters, o));
     const bool agree = !(o.max_chi2 > c.th);                                  // consensus_utils.cpp:17-21
     if (agree) {                                                              // :69-71
-        int rld = 0;
-        if (h->dim == 3) {
-            const double* res = cluster_result3(h, rld);
-            if (int rc = commit_accept(h, h->own_stream, k, c.lo, c.hi, nullptr, res, rld)) return rc;
-        } else {
-            const PoseArr X = cluster_result2(h);
-            if (int rc = commit_accept(h, h->own_stream, k, c.lo, c.hi, &X, nullptr, 0)) return rc;
-        }
+        if (int rc = commit_accept(h, h->own_stream, k, c.lo, c.hi, cluster_result(h))) return rc;
         HIPCHK(hipStreamSynchronize(h->own_stream));
     }
     h->handed[k] = 1;
@@ -4279,8 +4242,7 @@ static int grow_chain(ipc_engine* h, int cap)
         S.d_poses = S.own_poses;
     }
     for (auto& sl : h->slots) {
-        if (sl.s3) HIPCHK(sl.s3->reserve(cap - 1, std::max(256, std::min(h->N + 1, 16384)), 256));
-        if (sl.s2) HIPCHK(sl.s2->reserve(cap - 1, std::max(256, std::min(h->N + 1, 16384)), 256));
+        if (sl.s2 || sl.s3) HIPCHK(with_persist(h, sl, [&](auto& s) { return s.reserve(cap - 1, std::max(256, std::min(h->N + 1, 16384)), 256); }));
     }
     HIPCHK(hipStreamSynchronize(st));
     h->estride = nstride; h->vcap = cap;
@@ -4397,7 +4359,7 @@ extern "C" int ipc_incremental_counters(ipc_engine_t* h, ipc_incremental_counter
     out->host_solver_fallbacks = h->lm_fallbacks;
     out->lost_launches = h->persist_timeouts;
     out->relaunches = h->persist_relaunches;
-    out->literal_band_solves = (h->cluster ? h->cluster->literal_band_solves() : 0) + (h->cluster3 ? h->cluster3->literal_band_solves() : 0);
+    out->literal_band_solves = (h->cluster || h->cluster3) ? with_host(h, [](auto& s) { return s.literal_band_solves(); }) : 0;
     return IPC_OK;
 }
 
@@ -4443,26 +4405,14 @@ extern "C" int ipc_add_to_consensus(ipc_engine_t* h, int k)
     return IPC_OK;
 }
 
-static int download_poses(ipc_engine* h, const PoseArr& X, int n, double* poses_out)
+// device rows (first n columns; SE2: x y th of the five, SE3: all 12) -> host [n][3 | 12]
+static int download_poses(ipc_engine* h, PoseBlock X, int n, double* poses_out)
 {
-    std::vector<double> tmp(3 * (size_t)n);
-    HIPCHK(hipMemcpy(tmp.data(), X.x, sizeof(double) * n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(tmp.data() + n, X.y, sizeof(double) * n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(tmp.data() + 2 * (size_t)n, X.th, sizeof(double) * n, hipMemcpyDeviceToHost));
-    for (int i = 0; i < n; ++i) {
-        poses_out[3 * (size_t)i] = tmp[i]; poses_out[3 * (size_t)i + 1] = tmp[(size_t)n + i];
-        poses_out[3 * (size_t)i + 2] = tmp[2 * (size_t)n + i];
-    }
-    return IPC_OK;
-}
-
-// SE3: device [12][ld] (first n columns) -> host [n][12]
-static int download_poses3(ipc_engine* h, const double* d, int ld, int n, double* poses_out)
-{
-    std::vector<double> tmp(12 * (size_t)n);
-    HIPCHK(hipMemcpy2D(tmp.data(), sizeof(double) * n, d, sizeof(double) * ld, sizeof(double) * n, 12, hipMemcpyDeviceToHost));
+    const int nf = h->dim == 3 ? 12 : 3;
+    std::vector<double> tmp(nf * (size_t)n);
+    HIPCHK(hipMemcpy2D(tmp.data(), sizeof(double) * n, X.p, sizeof(double) * X.ld, sizeof(double) * n, nf, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; ++i)
-        for (int f = 0; f < 12; ++f) poses_out[12 * (size_t)i + f] = tmp[(size_t)f * n + i];
+        for (int f = 0; f < nf; ++f) poses_out[nf * (size_t)i + f] = tmp[(size_t)f * n + i];
     return IPC_OK;
 }
 
@@ -4472,8 +4422,7 @@ extern "C" int ipc_current_poses(ipc_engine_t* h, double* poses_out)
     if (int rc = ensure_incremental(h, "ipc_current_poses")) return rc;
     if (int rc = spec_quiesce(h, false)) return rc;
     HIPCHK(hipStreamSynchronize(h->own_stream));               // (vertices ipc_append_odometry is still writing)
-    if (h->dim == 3) return download_poses3(h, h->d_cur, h->vcap, h->V, poses_out);
-    return download_poses(h, pose_arr(h->d_cur, h->vcap), h->V, poses_out);
+    return download_poses(h, PoseBlock{h->d_cur, h->vcap}, h->V, poses_out);
 }
 
 extern "C" int ipc_final_optimize(ipc_engine_t* h, const uint8_t* accepted, int iterations, double* poses_out,
@@ -4511,22 +4460,13 @@ extern "C" int ipc_final_optimize(ipc_engine_t* h, const uint8_t* accepted, int 
         ClusterOut o;
         fill_info(info, 0, h->V - 1, 0, o);
         HIPCHK(hipStreamSynchronize(h->own_stream));
-        if (poses_out && h->dim == 3) return download_poses3(h, h->d_open, h->vcap, h->V, poses_out);
-        if (poses_out) return download_poses(h, pose_arr(h->d_open, h->vcap), h->V, poses_out);
+        if (poses_out) return download_poses(h, PoseBlock{h->d_open, h->vcap}, h->V, poses_out);
         return IPC_OK;
     }
     ClusterOut o;
-    if (h->dim == 3) {
-        HIPCHK(cluster_solve(h, h->d_chain1, h->d_open, 0, h->V - 1, members, iterations, o));
-        fill_info(info, 0, h->V - 1, (int)members.size(), o);
-        int rld = 0;
-        const double* res = cluster_result3(h, rld);
-        if (poses_out) return download_poses3(h, res, rld, h->V, poses_out);
-        return IPC_OK;
-    }
     HIPCHK(cluster_solve(h, h->d_chain1, h->d_open, 0, h->V - 1, members, iterations, o));
     fill_info(info, 0, h->V - 1, (int)members.size(), o);
-    if (poses_out) return download_poses(h, cluster_result2(h), h->V, poses_out);
+    if (poses_out) return download_poses(h, cluster_result(h), h->V, poses_out);
     return IPC_OK;
 }
 

@@ -591,6 +591,48 @@ def test_levenberg_retry_on_degenerate_information_incremental(oracle, mode):
     assert np.array_equal(eng.getMaxConsensusSet(), inc.consensus())
 
 
+def _degenerate_graph_se3():
+    """The SE3 counterpart of _degenerate_graph: three odometry edges keep only the translational 3 x 3 block of their
+    information (rank 3 of 6), one has none at all.  On the CPU oracle alone: 10 candidates, 6 accepted with max chi2
+    <= 2.41 and 4 rejected with max chi2 >= 131.9 against the thresholds 6.251 / 11.345, at most 56 iterations (caps 50
+    fast -- the one fast check takes 26 -- and 100 slow): no decision sits near a threshold or a cap."""
+    from ipc_amd import synth
+    g = synth.inject_outliers(synth.small_se3(seed=11, V=40, n_loops=6), 4, seed=3)
+    oi = g.odom_info.copy()
+    tt = [0, 1, 2, 6, 7, 11]                    # (0,0) (0,1) (0,2) (1,1) (1,2) (2,2) of the row-major upper triangle
+    for e in (5, 17, 29):
+        keep = oi[e][tt].copy()
+        oi[e] = 0.0
+        oi[e][tt] = keep
+    oi[22] = 0.0
+    g.odom_info = oi
+    return g
+
+
+@pytest.mark.parametrize("mode", ["persist", "host"])
+def test_levenberg_retry_on_degenerate_information_incremental_se3(oracle, mode):
+    """The host-driven solver's damped solve is one template for both pose types; this is its SE3 instance (dense
+    store of 6 L unknowns, the solution in the 6 ld scan workspace, gk3_literal_H's own block size)."""
+    from ipc_amd.consensus import Config
+    O = oracle
+    g = _degenerate_graph_se3()
+    cfg = Config()
+    eng = _engine(g, cfg, mode)
+    inc = O.IncrementalIPC(3, g.odom_meas, g.odom_info, cfg.s_factor, cfg.fast_reject_th, cfg.fast_reject_iter_base,
+                           cfg.slow_reject_th, cfg.slow_reject_iter_base, g.loop_ids, g.loop_meas, g.loop_info)
+    eng.reset()
+    damped = 0
+    for k in eng.candidate_order():
+        ok_ref, ref = inc.agreement_check(int(k))
+        ok, info = eng.agreementCheck(int(k), with_info=True)
+        assert ok == ok_ref, (k, ref, info.max_chi2)
+        assert abs(info.max_chi2 - ref["max_chi2"]) <= REL * max(abs(ref["max_chi2"]), 1e-9), (k, ref, info.max_chi2)
+        assert not (info.flags & 2)
+        damped += bool(info.flags & 4)
+    assert damped > 0
+    assert np.array_equal(eng.getMaxConsensusSet(), inc.consensus())
+
+
 def test_a_nan_edge_does_not_mask_an_edge_above_the_threshold(oracle):
     """src/consensus_utils.cpp:17-19 returns false as soon as ONE edge has chi2 > th; an edge whose chi2 is NaN is simply
     not above it.  One odometry edge with NaN information: every solve across it fails at once (NaN pivot, also under the
