@@ -419,6 +419,11 @@ typedef struct {
 int ipc_set_max_exact(ipc_engine_t* h, const uint64_t* d_bits, uint8_t* d_accepted, ipc_exact_report_t* report, void* stream);
 int ipc_run_exact(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accepted_out, uint8_t* multistart_out, ipc_exact_report_t* report);
 
+/* ---- resumed exact set, and the exact set in online matrix mode ---------------------------------------
+ * Three further entry points of the library, declared in a header of their own beside this one, which it needs for the
+ * handle and the online report and which includes it here (inside the extern "C" block, where there is one). */
+#include "ipc_amd_online_exact.h"
+
 /* Diagnostics of the last ipc_solve_rows(), ipc_run_online(), ipc_run_sweep() or ipc_run_batch(): number of solved cells, and their records. */
 int ipc_cell_count(ipc_engine_t* h, int* n_cells);
 int ipc_cell_info(ipc_engine_t* h, ipc_cell_info_t* out, int capacity);

@@ -40,6 +40,8 @@ SYMBOLS = [
     "ipc_set_max_multistart", "ipc_run_multistart",
     "ipc_set_max_exact", "ipc_run_exact",
 ]
+# every symbol include/ipc_amd_online_exact.h declares (checked by tests/test_exact_resume_cpu.py)
+SYMBOLS_ONLINE_EXACT = ["ipc_set_max_exact_resume", "ipc_run_online_exact", "ipc_online_exact_state"]
 
 
 class Params(C.Structure):
@@ -93,6 +95,12 @@ class MultistartReport(C.Structure):
 class ExactReport(C.Structure):
     _fields_ = [("live", C.c_int), ("multistart_size", C.c_int), ("size", C.c_int), ("upper_bound", C.c_int),
                 ("proven", C.c_int), ("subproblems", C.c_int), ("capped", C.c_int), ("steps", C.c_longlong)]
+
+
+class ExactResumeReport(C.Structure):
+    _fields_ = [("first", C.c_int), ("live", C.c_int), ("newcomers", C.c_int), ("size_before", C.c_int),
+                ("multistart_size", C.c_int), ("size", C.c_int), ("upper_bound", C.c_int), ("proven", C.c_int),
+                ("changed", C.c_int), ("subproblems", C.c_int), ("capped", C.c_int), ("steps", C.c_longlong)]
 
 
 CELL_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("lo", "<i4"), ("hi", "<i4"), ("max_chi2", "<f8"),
@@ -150,6 +158,9 @@ def load():
     lib.ipc_run_multistart.argtypes = [vp, vp, vp, vp, vp, C.POINTER(MultistartReport)]
     lib.ipc_set_max_exact.argtypes = [vp, vp, vp, C.POINTER(ExactReport), vp]
     lib.ipc_run_exact.argtypes = [vp, vp, vp, vp, C.POINTER(ExactReport)]
+    lib.ipc_set_max_exact_resume.argtypes = [vp, vp, ip, vp, C.POINTER(ExactResumeReport), vp]
+    lib.ipc_run_online_exact.argtypes = [vp, vp, vp, vp, C.POINTER(OnlineReport), C.POINTER(ExactResumeReport)]
+    lib.ipc_online_exact_state.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
     lib.ipc_run_sharded.argtypes =[C.POINTER(vp), ip, vp, vp]
     lib.ipc_run_set_only.argtypes = [vp, vp, C.POINTER(ip)]
     lib.ipc_cell_count.argtypes = [vp, C.POINTER(ip)]

@@ -152,6 +152,28 @@ class IPC:
         """Forget the online matrix (ipc_online_reset): the next run_online solves every cell."""
         capi.check(self.lib.ipc_online_reset(self.h))
 
+    def run_online_exact(self, want_bits=False):
+        """ipc_run_online_exact: the update of run_online(), then the exact set of the stored matrix, resumed from the proven set
+        the engine holds where it has one.  Returns (accepted [N] uint8, greedy [N] uint8, online report dict, report dict), with
+        want_bits (bits [N, words] uint64, accepted, greedy, online report, report); bits, greedy and the online report are
+        those of run_online().  report["proven"] = 1: accepted is a maximum consistent set of report["size"] members.
+        getMaxConsensusSet() is left as it was."""
+        acc = np.zeros(self.N, dtype=np.uint8)
+        greedy = np.zeros(self.N, dtype=np.uint8)
+        bits = np.zeros((self.N, self.words), dtype=np.uint64) if want_bits else None
+        o, r = capi.OnlineReport(), capi.ExactResumeReport()
+        capi.check(self.lib.ipc_run_online_exact(self.h, _p(bits) if want_bits else None, _p(acc), _p(greedy), C.byref(o), C.byref(r)))
+        online = {k: getattr(o, k) for k, _ in capi.OnlineReport._fields_}
+        report = {k: getattr(r, k) for k, _ in capi.ExactResumeReport._fields_}
+        return (bits, acc, greedy, online, report) if want_bits else (acc, greedy, online, report)
+
+    @property
+    def online_exact_state(self):
+        """(covered, proven) of the exact set the engine holds for run_online_exact (ipc_online_exact_state); (0, 0): none."""
+        c, p = C.c_int(0), C.c_int(0)
+        capi.check(self.lib.ipc_online_exact_state(self.h, C.byref(c), C.byref(p)))
+        return c.value, p.value
+
     def reserve_candidates(self, n):
         """Room for n candidates up front, in the candidate arrays and the online matrix (ipc_reserve_candidates)."""
         capi.check(self.lib.ipc_reserve_candidates(self.h, int(n)))
@@ -323,6 +345,13 @@ class IPC:
         r = capi.ExactReport()
         capi.check(self.lib.ipc_set_max_exact(self.h, C.c_void_p(d_bits_ptr), C.c_void_p(d_accepted_ptr), C.byref(r), C.c_void_p(stream)))
         return {k: getattr(r, k) for k, _ in capi.ExactReport._fields_}
+
+    def set_max_exact_resume(self, d_bits_ptr, first, d_accepted_ptr, stream=0):
+        """ipc_set_max_exact_resume on device pointers; blocks until the search is over and returns the report as a dict."""
+        r = capi.ExactResumeReport()
+        capi.check(self.lib.ipc_set_max_exact_resume(self.h, C.c_void_p(d_bits_ptr), int(first), C.c_void_p(d_accepted_ptr), C.byref(r),
+                                                     C.c_void_p(stream)))
+        return {k: getattr(r, k) for k, _ in capi.ExactResumeReport._fields_}
 
     # ---- diagnostics ----------------------------------------------------------------------
     def cell_info(self):

@@ -820,6 +820,14 @@ struct ipc_engine {
     DevBuf<unsigned long long> d_ex_ws; size_t ex_ws_cap = 0;
     DevBuf<unsigned short> d_ex_clq; size_t ex_clq_cap = 0;
     unsigned ex_step_cap = 1u << 20;                   // IPC_EXACT_STEP_CAP: steps after which a subproblem gives up
+    // Resumed exact set (ipc_set_max_exact_resume): the info words and the NEW mask (exact_resume_kernels.hpp),
+    // the root list [N]; flags, sizes, steps, stacks and cliques are those above, by root rank.  ipc_run_online_exact holds its
+    // set in d_on_exact [on_ccap] (sized and moved with the online storage), proven over the first on_ex_cov candidates.
+    DevBuf<int> d_exr_info, d_exr_roots; int exr_roots_cap = 0;
+    DevBuf<unsigned long long> d_exr_new;
+    DevBuf<unsigned char> d_on_exact;
+    int on_ex_cov = 0, on_ex_proven = 0;
+    bool on_ex_resume = true;                          // IPC_ONLINE_EXACT_RESUME=0: every ipc_run_online_exact searches the whole graph (A/B)
     // incremental mode / final map (SE2)
     std::vector<double> h_odom_meas, h_odom_info;      // file values, for the un-scaled chain
     std::vector<int> h_from, h_to, cns;
@@ -1126,6 +1134,7 @@ extern "C" int ipc_create(int dim, int n_vertices, const double* odom_meas, cons
     if (const char* bc = getenv("IPC_BATCH_CHUNK")) { if (*bc) h->batch_chunk = std::max(0, atoi(bc)); }
     if (const char* bb = getenv("IPC_BATCH_BUDGET")) { if (*bb) h->batch_budget = (size_t)std::max(0ll, atoll(bb)); }
     if (const char* mw = getenv("IPC_MULTISTART_REG_WORDS")) { if (*mw) h->ms_reg_words = std::min(2, std::max(0, atoi(mw))); }
+    if (const char* er = getenv("IPC_ONLINE_EXACT_RESUME")) { if (*er) h->on_ex_resume = atoi(er) != 0; }
     if (const char* ec = getenv("IPC_EXACT_STEP_CAP")) { if (*ec) h->ex_step_cap = (unsigned)std::min(1ll << 30, std::max(1ll, atoll(ec))); }
     if (const char* sf = getenv("IPC_SLOW_FIRST")) { if (*sf) h->slow_first_iterations = std::max(0, atoi(sf)); }
     if (const char* rb = getenv("IPC_ROW_BALANCE")) {
@@ -1236,6 +1245,7 @@ static void free_candidates(ipc_engine* h)
     h->retired.clear();
     h->N = 0; h->cstride = 0; h->order_stale = false; h->cand_event = false;
     h->on_cov = 0;                                       // (the online matrix's storage stays; its content is that of another list)
+    h->on_ex_cov = h->on_ex_proven = 0;
     h->sw_valid = h->info_from_sweep = false;            // (and so does the sweep's: its first pass is that of another list)
 }
 
@@ -1669,6 +1679,7 @@ __device__ __forceinline__ int slot_of_cell(const unsigned* slot_off, int nslots
 #include "batch_kernels.hpp"
 #include "multistart_kernels.hpp"
 #include "exact_kernels.hpp"
+#include "exact_resume_kernels.hpp"
 // Failed cells -> list (host-driven Levenberg retry, rare); borderline cells -> the compact list of their slot (lit_cells /
 // lit_idx at the slot's own offset: a slot has room for all of its cells), counted per slot in recount[0 .. nslots).
 __global__ void k_collect_failed(int ncells, const int4* meta, const double* chi, const int2* cells, double fast_th,
@@ -2213,12 +2224,9 @@ static int ensure_multistart_scratch(ipc_engine* h, int N, size_t need)
     return IPC_OK;
 }
 
-extern "C" int ipc_set_max_multistart(ipc_engine_t* h, const uint64_t* d_bits, uint8_t* d_accepted, int32_t* d_sizes, void* stream)
+// `stride` = words per stored row of d_bits (the online matrix: its capacity stride); P is [N][words] whatever the stride
+static int set_max_multistart(ipc_engine* h, const uint64_t* d_bits, int stride, uint8_t* d_accepted, int32_t* d_sizes, hipStream_t st)
 {
-    if (!h || !d_bits || !d_accepted) return fail(IPC_ERR_ARG, "ipc_set_max_multistart: NULL argument");
-    if (h->N <= 0) return fail(IPC_ERR_STATE, "ipc_set_max_multistart: no candidates set");
-    HIPCHK(hipSetDevice(h->device));
-    hipStream_t st = stream ? (hipStream_t)stream : h->own_stream;
     const int N = h->N, words = (N + 63) / 64;
     const size_t row_bytes = sizeof(unsigned long long) * words;
     if (row_bytes > 60 * 1024) return fail(IPC_ERR_LIMIT, "ipc_set_max_multistart: N=%d exceeds the LDS-resident mask", N);
@@ -2227,9 +2235,9 @@ extern "C" int ipc_set_max_multistart(ipc_engine_t* h, const uint64_t* d_bits, u
     const int cap = h->ms_vec_cap;
     int* live = h->d_ms_vec; int* pos = live + cap; int* sz = pos + cap;
     const unsigned long long* C = (const unsigned long long*)d_bits;
-    hipLaunchKernelGGL(k_ms_live, dim3(1), dim3(1024), 0, st, N, words, (const int*)h->d_order, C, live, pos, h->d_ms_info);
+    hipLaunchKernelGGL(k_ms_live, dim3(1), dim3(1024), 0, st, N, stride, (const int*)h->d_order, C, live, pos, h->d_ms_info);
     const dim3 grid((N + kMsWaves - 1) / kMsWaves), block(64 * kMsWaves);
-    hipLaunchKernelGGL(k_ms_compact, grid, block, 0, st, words, C, (const int*)live, (const int*)h->d_ms_info, h->d_ms_P);
+    hipLaunchKernelGGL(k_ms_compact, grid, block, 0, st, words, stride, C, (const int*)live, (const int*)h->d_ms_info, h->d_ms_P);
     // cand in registers while a lane's share of the words is within the knob, else in LDS: as many waves per workgroup as
     // 60 KB of slices hold, four at the most (one at the N limit)
     const int per_lane = (words + 63) / 64;
@@ -2246,6 +2254,14 @@ extern "C" int ipc_set_max_multistart(ipc_engine_t* h, const uint64_t* d_bits, u
                        (const int*)pos, (const int*)sz, h->d_ms_info, d_accepted, d_sizes);
     HIPCHK(hipGetLastError());
     return IPC_OK;
+}
+
+extern "C" int ipc_set_max_multistart(ipc_engine_t* h, const uint64_t* d_bits, uint8_t* d_accepted, int32_t* d_sizes, void* stream)
+{
+    if (!h || !d_bits || !d_accepted) return fail(IPC_ERR_ARG, "ipc_set_max_multistart: NULL argument");
+    if (h->N <= 0) return fail(IPC_ERR_STATE, "ipc_set_max_multistart: no candidates set");
+    HIPCHK(hipSetDevice(h->device));
+    return set_max_multistart(h, d_bits, (h->N + 63) / 64, d_accepted, d_sizes, stream ? (hipStream_t)stream : h->own_stream);
 }
 
 extern "C" int ipc_run_multistart(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accepted_out, uint8_t* greedy_out, int32_t* sizes_out,
@@ -2295,11 +2311,11 @@ constexpr size_t kExPoolBytes = (size_t)2 << 30;       // ... down to kExPoolFlo
 
 // The multi-start set into d_accepted, UB0, then -- unless that already closes the bracket -- the search and the pick.  Blocks the
 // host twice: once to size the workspace from n, LB and UB0, once for the report.  ms_host, unless NULL, gets the multi-start set.
-static int set_max_exact(ipc_engine* h, const uint64_t* d_bits, uint8_t* d_accepted, ipc_exact_report_t* report, hipStream_t st,
-                         uint8_t* ms_host)
+static int set_max_exact(ipc_engine* h, const uint64_t* d_bits, int stride, uint8_t* d_accepted, ipc_exact_report_t* report,
+                         hipStream_t st, uint8_t* ms_host)
 {
     const int N = h->N, words = (N + 63) / 64;
-    if (int rc = ipc_set_max_multistart(h, d_bits, d_accepted, nullptr, st)) return rc;
+    if (int rc = set_max_multistart(h, d_bits, stride, d_accepted, nullptr, st)) return rc;
     if (N > h->ex_vec_cap) {
         h->ex_vec_cap = 0;
         HIPCHK(h->d_ex_vec.alloc(3 * (size_t)N));
@@ -2373,7 +2389,7 @@ extern "C" int ipc_set_max_exact(ipc_engine_t* h, const uint64_t* d_bits, uint8_
     if (h->N <= 0) return fail(IPC_ERR_STATE, "ipc_set_max_exact: no candidates set");
     if (h->N > kExLimitN) return fail(IPC_ERR_LIMIT, "ipc_set_max_exact: N=%d exceeds %d candidates", h->N, kExLimitN);
     HIPCHK(hipSetDevice(h->device));
-    return set_max_exact(h, d_bits, d_accepted, report, stream ? (hipStream_t)stream : h->own_stream, nullptr);
+    return set_max_exact(h, d_bits, (h->N + 63) / 64, d_accepted, report, stream ? (hipStream_t)stream : h->own_stream, nullptr);
 }
 
 extern "C" int ipc_run_exact(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accepted_out, uint8_t* multistart_out, ipc_exact_report_t* report)
@@ -2390,11 +2406,125 @@ extern "C" int ipc_run_exact(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accep
     if (rc) return rc;
     rc = ipc_assemble_matrix(h, h->d_upper, 1, h->d_bits, h->own_stream);
     if (rc) return rc;
-    rc = set_max_exact(h, h->d_bits, h->d_ms_acc, report, h->own_stream, multistart_out);
+    rc = set_max_exact(h, h->d_bits, words, h->d_ms_acc, report, h->own_stream, multistart_out);
     if (rc) return rc;
     if (bits_out) HIPCHK(hipMemcpy(bits_out, h->d_bits, sizeof(uint64_t) * need, hipMemcpyDeviceToHost));
     if (accepted_out) HIPCHK(hipMemcpy(accepted_out, h->d_ms_acc, (size_t)N, hipMemcpyDeviceToHost));
     return IPC_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// resumed exact set: d_accepted holds a maximum clique of the candidates < first, only the newcomers are searched
+// ------------------------------------------------------------------------------------------
+// The multi-start set of the whole matrix into the engine's d_ms_acc, the checks and NEW's figures, then -- unless the set handed
+// in is invalid (IPC_ERR_ARG, nothing written) or the bracket is closed already -- the search over the newcomer roots and the
+// pick.  Blocks the host twice, as set_max_exact.
+static int set_max_exact_resume(ipc_engine* h, const uint64_t* d_bits, int stride, int first, uint8_t* d_accepted,
+                                ipc_exact_resume_report_t* report, hipStream_t st)
+{
+    const int N = h->N, words = (N + 63) / 64;
+    if (int rc = ensure_multistart_scratch(h, N, (size_t)N * words)) return rc;
+    if (int rc = set_max_multistart(h, d_bits, stride, h->d_ms_acc, nullptr, st)) return rc;
+    if (N > h->ex_vec_cap) {
+        h->ex_vec_cap = 0;
+        HIPCHK(h->d_ex_vec.alloc(3 * (size_t)N));
+        h->ex_vec_cap = N;
+    }
+    if (N > h->exr_roots_cap) {
+        h->exr_roots_cap = 0;
+        HIPCHK(h->d_exr_roots.alloc((size_t)N));
+        h->exr_roots_cap = N;
+    }
+    if (!h->d_exr_info) HIPCHK(h->d_exr_info.alloc(kExrInfo));
+    if (!h->d_exr_new) HIPCHK(h->d_exr_new.alloc((kExLimitN + 63) / 64));
+    const unsigned long long* P = h->d_ms_P;
+    const int* ms_info = h->d_ms_info;
+    const int* live = h->d_ms_vec; const int* pos = live + h->ms_vec_cap;
+    int* info = h->d_exr_info;
+    const bool one = words <= 64;
+    if (one)
+        hipLaunchKernelGGL(k_exr_prepare<1>, dim3(1), dim3(1024), 0, st, N, first, words, P, live, pos, ms_info, (const unsigned char*)d_accepted,
+                           (unsigned long long*)h->d_exr_new, (int*)h->d_exr_roots, info);
+    else
+        hipLaunchKernelGGL(k_exr_prepare<2>, dim3(1), dim3(1024), 0, st, N, first, words, P, live, pos, ms_info, (const unsigned char*)d_accepted,
+                           (unsigned long long*)h->d_exr_new, (int*)h->d_exr_roots, info);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    int ms[kMsInfo], ex[kExrInfo] = {0};
+    HIPCHK(hipMemcpy(ms, h->d_ms_info, sizeof(ms), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ex, info, sizeof(int) * 4, hipMemcpyDeviceToHost));
+    if (!ex[0])
+        return fail(IPC_ERR_ARG, "ipc_set_max_exact_resume: d_accepted is not a set of pairwise consistent live candidates in front of first=%d", first);
+    const int n = ms[0], lb = ms[1], w0 = ex[1], m = ex[2], c = ex[3];
+    const int b0 = std::max(w0, lb), ub = std::min(n, w0 + c);
+    const bool search = m > 0 && b0 < ub;
+    ipc_exact_resume_report_t rep{};
+    rep.first = first; rep.live = n; rep.newcomers = m; rep.size_before = w0; rep.multistart_size = lb;
+    if (search) {
+        const int levels = ub;
+        const int level_words = 64 * (one ? 1 : 2) + (n + 3) / 4 + 1;
+        const size_t slice_words = (size_t)levels * level_words + (size_t)(levels + 1) / 2;
+        int pool = std::min(kExPool, (m + kExWaves - 1) / kExWaves * kExWaves);
+        while (pool > kExPoolFloor && pool * slice_words * 8 > kExPoolBytes) pool /= 2;
+        const size_t need_ws = pool * slice_words, need_clq = (size_t)m * levels;
+        if (need_ws > h->ex_ws_cap || need_clq > h->ex_clq_cap) {
+            size_t mem_free = 0, mem_total = 0;
+            HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
+            const size_t bytes = (need_ws > h->ex_ws_cap ? need_ws * 8 : 0) + (need_clq > h->ex_clq_cap ? need_clq * 2 : 0);
+            if (bytes > mem_free / 4)
+                return fail(IPC_ERR_LIMIT, "ipc_set_max_exact_resume: a search of %d levels over %d newcomers needs %zu MB, a quarter of the free memory is %zu MB",
+                            levels, m, bytes >> 20, mem_free >> 22);
+        }
+        if (need_ws > h->ex_ws_cap) {
+            h->ex_ws_cap = 0;
+            HIPCHK(h->d_ex_ws.alloc(need_ws));
+            h->ex_ws_cap = need_ws;
+        }
+        if (need_clq > h->ex_clq_cap) {
+            h->ex_clq_cap = 0;
+            HIPCHK(h->d_ex_clq.alloc(need_clq));
+            h->ex_clq_cap = need_clq;
+        }
+        const int cap = h->ex_vec_cap;
+        int* flag = h->d_ex_vec; int* size = flag + cap; unsigned* steps = (unsigned*)(size + cap);
+        const dim3 grid(pool / kExWaves), block(64 * kExWaves);
+        if (one)
+            hipLaunchKernelGGL(k_exr_search<1>, grid, block, 0, st, words, levels, level_words, slice_words, h->ex_step_cap, P, ms_info, info,
+                               (const unsigned long long*)h->d_exr_new, (const int*)h->d_exr_roots, (unsigned long long*)h->d_ex_ws, flag, size,
+                               steps, (unsigned short*)h->d_ex_clq);
+        else
+            hipLaunchKernelGGL(k_exr_search<2>, grid, block, 0, st, words, levels, level_words, slice_words, h->ex_step_cap, P, ms_info, info,
+                               (const unsigned long long*)h->d_exr_new, (const int*)h->d_exr_roots, (unsigned long long*)h->d_ex_ws, flag, size,
+                               steps, (unsigned short*)h->d_ex_clq);
+    }
+    {
+        const int cap = h->ex_vec_cap;
+        const int* flag = h->d_ex_vec; const int* size = flag + cap; const unsigned* steps = (const unsigned*)(size + cap);
+        hipLaunchKernelGGL(k_exr_pick, dim3(1), dim3(1024), 0, st, N, search ? ub : 1, search ? 1 : 0, live, ms_info, flag, size, steps,
+                           (const unsigned short*)h->d_ex_clq, (const unsigned char*)h->d_ms_acc, info, d_accepted);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(ex, info, sizeof(ex), hipMemcpyDeviceToHost));
+    rep.subproblems = ex[7]; rep.capped = ex[8];
+    rep.steps = (long long)(((unsigned long long)(unsigned)ex[10] << 32) | (unsigned)ex[9]);
+    rep.changed = ex[11];
+    rep.size = ex[5];
+    if (rep.capped == 0) { rep.proven = 1; rep.upper_bound = rep.size; }
+    else { rep.proven = 0; rep.upper_bound = ub; }
+    if (report) *report = rep;
+    return IPC_OK;
+}
+
+extern "C" int ipc_set_max_exact_resume(ipc_engine_t* h, const uint64_t* d_bits, int first, uint8_t* d_accepted,
+                                        ipc_exact_resume_report_t* report, void* stream)
+{
+    if (!h || !d_bits || !d_accepted) return fail(IPC_ERR_ARG, "ipc_set_max_exact_resume: NULL argument");
+    if (h->N <= 0) return fail(IPC_ERR_STATE, "ipc_set_max_exact_resume: no candidates set");
+    if (h->N > kExLimitN) return fail(IPC_ERR_LIMIT, "ipc_set_max_exact_resume: N=%d exceeds %d candidates", h->N, kExLimitN);
+    if (first < 0 || first > h->N) return fail(IPC_ERR_ARG, "ipc_set_max_exact_resume: first=%d (0 .. N=%d)", first, h->N);
+    HIPCHK(hipSetDevice(h->device));
+    return set_max_exact_resume(h, d_bits, (h->N + 63) / 64, first, d_accepted, report, stream ? (hipStream_t)stream : h->own_stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2407,7 +2537,7 @@ static int grow_online(ipc_engine* h, int cap)
     const int wcap = cap / 64, M = h->on_cov;
     hipStream_t st = h->own_stream;
     DevBuf<unsigned long long> n_upper, n_bits, n_mask;
-    DevBuf<unsigned char> n_acc; DevBuf<int> n_live;
+    DevBuf<unsigned char> n_acc, n_exact; DevBuf<int> n_live;
     const size_t mat = sizeof(unsigned long long) * (size_t)cap * wcap;
     size_t mem_free = 0, mem_total = 0;                  // (quadratic in the capacity: 2 x 512 MB at 65 536 candidates -- refused before anything is allocated)
     HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
@@ -2417,11 +2547,13 @@ static int grow_online(ipc_engine* h, int cap)
     HIPCHK(n_bits.alloc((size_t)cap * wcap));
     HIPCHK(n_mask.alloc(wcap));
     HIPCHK(n_acc.alloc(cap));
+    HIPCHK(n_exact.alloc(cap));
     HIPCHK(n_live.alloc((size_t)cap + 1));
     HIPCHK(hipMemsetAsync(n_upper, 0, mat, st));
     HIPCHK(hipMemsetAsync(n_bits, 0, mat, st));
     HIPCHK(hipMemsetAsync(n_mask, 0, sizeof(unsigned long long) * wcap, st));
     HIPCHK(hipMemsetAsync(n_acc, 0, (size_t)cap, st));
+    HIPCHK(hipMemsetAsync(n_exact, 0, (size_t)cap, st));
     HIPCHK(hipMemsetAsync(n_live, 0, sizeof(int) * ((size_t)cap + 1), st));
     if (M > 0) {
         const size_t opitch = sizeof(unsigned long long) * h->on_wcap, npitch = sizeof(unsigned long long) * wcap;
@@ -2429,12 +2561,14 @@ static int grow_online(ipc_engine* h, int cap)
         HIPCHK(hipMemcpy2DAsync(n_bits, npitch, h->d_on_bits, opitch, opitch, M, hipMemcpyDeviceToDevice, st));
         HIPCHK(hipMemcpyAsync(n_mask, h->d_on_mask, opitch, hipMemcpyDeviceToDevice, st));
         HIPCHK(hipMemcpyAsync(n_acc, h->d_on_acc, (size_t)M, hipMemcpyDeviceToDevice, st));
+        if (h->on_ex_cov > 0) HIPCHK(hipMemcpyAsync(n_exact, h->d_on_exact, (size_t)h->on_ex_cov, hipMemcpyDeviceToDevice, st));
         HIPCHK(hipMemcpyAsync(n_live, h->d_on_live, sizeof(int) * (size_t)M, hipMemcpyDeviceToDevice, st));
         HIPCHK(hipMemcpyAsync(n_live + cap, h->d_on_live + h->on_ccap, sizeof(int), hipMemcpyDeviceToDevice, st));
     }
     retire(h, h->d_on_upper); retire(h, h->d_on_bits); retire(h, h->d_on_mask); retire(h, h->d_on_acc); retire(h, h->d_on_live);
+    retire(h, h->d_on_exact);
     h->d_on_upper = std::move(n_upper); h->d_on_bits = std::move(n_bits); h->d_on_mask = std::move(n_mask);
-    h->d_on_acc = std::move(n_acc); h->d_on_live = std::move(n_live);
+    h->d_on_acc = std::move(n_acc); h->d_on_live = std::move(n_live); h->d_on_exact = std::move(n_exact);
     h->on_ccap = cap; h->on_wcap = wcap;
     ++h->online_growths;
     return IPC_OK;
@@ -2464,6 +2598,7 @@ extern "C" int ipc_online_reset(ipc_engine_t* h)
 {
     if (!h) return fail(IPC_ERR_ARG, "ipc_online_reset: NULL handle");
     h->on_cov = 0;                                       // (the next ipc_run_online clears the storage before it writes)
+    h->on_ex_cov = h->on_ex_proven = 0;                  // (and the next ipc_run_online_exact searches the whole graph)
     return IPC_OK;
 }
 
@@ -2531,6 +2666,48 @@ extern "C" int ipc_run_online(ipc_engine_t* h, uint64_t* bits_out, uint8_t* acce
                            hipMemcpyDeviceToHost));
     if (accepted_out) HIPCHK(hipMemcpy(accepted_out, h->d_on_acc, (size_t)N, hipMemcpyDeviceToHost));
     if (report) *report = rep;
+    return IPC_OK;
+}
+
+// ipc_run_online's update, then the exact set of the stored matrix: resumed from the held set where that is proven over a
+// prefix of the list, the whole search of 3.7 otherwise.
+extern "C" int ipc_run_online_exact(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accepted_out, uint8_t* greedy_out,
+                                    ipc_online_report_t* online_report, ipc_exact_resume_report_t* report)
+{
+    if (!h) return fail(IPC_ERR_ARG, "ipc_run_online_exact: NULL handle");
+    if (h->N <= 0) return fail(IPC_ERR_STATE, "ipc_run_online_exact: no candidates set");
+    if (h->N > kExLimitN) return fail(IPC_ERR_LIMIT, "ipc_run_online_exact: N=%d exceeds %d candidates", h->N, kExLimitN);
+    if (int rc = ipc_run_online(h, bits_out, greedy_out, online_report)) return rc;
+    const int N = h->N, stride = h->on_wcap;
+    hipStream_t st = h->own_stream;
+    const uint64_t* bits = (const uint64_t*)(const unsigned long long*)h->d_on_bits;
+    ipc_exact_resume_report_t rep{};
+    const bool resume = h->on_ex_resume && h->on_ex_proven && h->on_ex_cov > 0 && h->on_ex_cov <= N;
+    const int first = resume ? h->on_ex_cov : 0;
+    h->on_ex_cov = h->on_ex_proven = 0;                  // (a call that fails part way leaves no claim behind)
+    if (resume) {
+        // (bytes behind the covered prefix may be those of an earlier, longer list)
+        if (first < N) HIPCHK(hipMemsetAsync(h->d_on_exact + first, 0, (size_t)(N - first), st));
+        if (int rc = set_max_exact_resume(h, bits, stride, first, h->d_on_exact, &rep, st)) return rc;
+    } else {
+        ipc_exact_report_t ex{};
+        if (int rc = set_max_exact(h, bits, stride, h->d_on_exact, &ex, st, nullptr)) return rc;
+        rep.first = 0; rep.live = rep.newcomers = ex.live; rep.size_before = 0; rep.multistart_size = ex.multistart_size;
+        rep.size = ex.size; rep.upper_bound = ex.upper_bound; rep.proven = ex.proven; rep.changed = ex.size > 0 ? 1 : 0;
+        rep.subproblems = ex.subproblems; rep.capped = ex.capped; rep.steps = ex.steps;
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    h->on_ex_cov = N; h->on_ex_proven = rep.proven;
+    if (accepted_out) HIPCHK(hipMemcpy(accepted_out, h->d_on_exact, (size_t)N, hipMemcpyDeviceToHost));
+    if (report) *report = rep;
+    return IPC_OK;
+}
+
+extern "C" int ipc_online_exact_state(ipc_engine_t* h, int* covered, int* proven)
+{
+    if (!h) return fail(IPC_ERR_ARG, "ipc_online_exact_state: NULL handle");
+    if (covered) *covered = h->on_ex_cov;
+    if (proven) *proven = h->on_ex_proven;
     return IPC_OK;
 }
 

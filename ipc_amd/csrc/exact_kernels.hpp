@@ -11,6 +11,7 @@
 //                    LB and the subproblem's OWN finds only -- what a subproblem explores, finds and counts does not depend
 //                    on which wave runs it, on the size of the pool or on any other subproblem.
 //   k_ex_pick        one workgroup: (max size, min q) over the subproblems in a fixed order, their counts, the outputs
+// The search of one subproblem is ex_subproblem<R>, which k_exr_search (exact_resume_kernels.hpp) calls as well.
 // A candidate set is a bit set spread over the lanes as in k_ms_greedy_reg: lane l holds the words l, l + 64, .. (R of them).
 // A node colours its set (repeat: open a class, take the lowest position left, strike its neighbours from the sweep), lists the
 // vertices whose colour could still beat the best clique, in colour order, and branches from the end of that list; a child
@@ -111,7 +112,81 @@ __global__ __launch_bounds__(64) void k_ex_bound(int words, const unsigned long 
     if (lane == 0) { ex_info[0] = k; ex_info[1] = 0; }
 }
 
-// levels: the depth of a wave's stack; level_words: 64 R + ceil(n / 4) + 1 words of 8 bytes; slice_words: levels x level_words + the path
+// The depth-first search of one subproblem, shared by k_ex_search and k_exr_search (exact_resume_kernels.hpp): the cliques that
+// contain `root` and members of S (the root's candidate set, as the caller restricted it), looking for more than `lb` members.
+// Returns the steps made; `go` false: the cap was hit; `found`: a clique of `best` > lb members went to out[0 .. best).
+// levels: the depth of a wave's stack; level_words: 64 R + ceil(n / 4) + 1 words of 8 bytes; the path lies behind the levels.
+template <int R>
+__device__ __forceinline__ unsigned ex_subproblem(unsigned long long (&S)[R], int lane, int root, int lb, int nw, int words, int levels,
+                                                  int level_words, unsigned cap, const unsigned long long* P, unsigned long long* slice,
+                                                  int* path, unsigned short* out, int& best, bool& found, bool& go)
+{
+    unsigned long long C[R];
+    // level d: the clique so far is root, path[0 .. d); S = its candidates still to branch on or to keep for the children
+    int d = 0, cnt = 0, k = 0;
+    unsigned steps = 0;
+    bool entering = true;
+    best = lb; go = true; found = false;
+    for (;;) {
+        unsigned long long* level = slice + (size_t)d * level_words;
+        unsigned short* list = (unsigned short*)(level + 64 * R);
+        int* counters = (int*)(level + level_words - 1);
+        if (entering) {
+            k = ex_colour<R>(S, lane, nw, words, P, best - (d + 1), list, cnt, steps, cap, go);
+            if (!go) break;
+            entering = false;
+        }
+        if (cnt == 0 || d + 1 + k <= best) {                     // nothing left here that could beat the best: back up
+            if (d == 0) break;
+            --d;
+            ex_fence();
+            level = slice + (size_t)d * level_words;
+            counters = (int*)(level + level_words - 1);
+#pragma unroll
+            for (int r = 0; r < R; ++r) S[r] = level[lane + 64 * r];
+            cnt = counters[0];
+            k = counters[1];
+            continue;
+        }
+        ex_fence();
+        const unsigned short e = list[cnt - 1];
+        const int v = e & 0x7fff;
+        --cnt;
+        const int k_next = k - (e >> 15);
+        if (steps >= cap) { go = false; break; }
+        ++steps;
+        ex_clear<R>(S, lane, v);
+        {
+            const unsigned long long* row = P + (size_t)v * words;
+#pragma unroll
+            for (int r = 0; r < R; ++r) C[r] = lane + 64 * r < nw ? S[r] & row[lane + 64 * r] : 0ull;
+        }
+        bool empty = true;
+#pragma unroll
+        for (int r = 0; r < R; ++r) empty = empty && __ballot(C[r] != 0ull) == 0ull;
+        if (empty) {                                             // a maximal clique of d + 2: the first of its size wins
+            if (d + 2 > best && d + 2 <= levels) {
+                best = d + 2;
+                found = true;
+                for (int j = lane; j < d; j += 64) out[1 + j] = (unsigned short)path[j];
+                if (lane == 0) { out[0] = (unsigned short)root; out[d + 1] = (unsigned short)v; }
+            }
+            k = k_next;
+            continue;
+        }
+        if (d + 1 >= levels) { go = false; break; }              // (cannot happen while the bound on the clique number holds)
+#pragma unroll
+        for (int r = 0; r < R; ++r) level[lane + 64 * r] = S[r];
+        if (lane == 0) { counters[0] = cnt; counters[1] = k_next; path[d] = v; }
+        ++d;
+#pragma unroll
+        for (int r = 0; r < R; ++r) S[r] = C[r];
+        entering = true;
+    }
+    return steps;
+}
+
+// slice_words: levels x level_words + the path
 template <int R>
 __global__ __launch_bounds__(64 * kExWaves) void k_ex_search(int words, int levels, int level_words, size_t slice_words, unsigned cap,
                                                              const unsigned long long* P, const int* ms_info, int* ex_info,
@@ -127,7 +202,7 @@ __global__ __launch_bounds__(64 * kExWaves) void k_ex_search(int words, int leve
         if (lane == 0) q = atomicAdd(&ex_info[1], 1);
         q = __builtin_amdgcn_readfirstlane(q);
         if (q >= n) return;
-        unsigned long long S[R], C[R];
+        unsigned long long S[R];
         int size0 = 0;
         {
             const unsigned long long* row = P + (size_t)q * words;
@@ -144,67 +219,10 @@ __global__ __launch_bounds__(64 * kExWaves) void k_ex_search(int words, int leve
             if (lane == 0) { sub_flag[q] = 0; sub_size[q] = 0; sub_steps[q] = 0u; }
             continue;
         }
-        // level d: the clique so far is q, path[0 .. d); S = its candidates still to branch on or to keep for the children
-        int best = lb, d = 0, cnt = 0, k = 0;
-        unsigned steps = 0;
-        bool go = true, found = false, entering = true;
-        for (;;) {
-            unsigned long long* level = slice + (size_t)d * level_words;
-            unsigned short* list = (unsigned short*)(level + 64 * R);
-            int* counters = (int*)(level + level_words - 1);
-            if (entering) {
-                k = ex_colour<R>(S, lane, nw, words, P, best - (d + 1), list, cnt, steps, cap, go);
-                if (!go) break;
-                entering = false;
-            }
-            if (cnt == 0 || d + 1 + k <= best) {                     // nothing left here that could beat the best: back up
-                if (d == 0) break;
-                --d;
-                ex_fence();
-                level = slice + (size_t)d * level_words;
-                counters = (int*)(level + level_words - 1);
-#pragma unroll
-                for (int r = 0; r < R; ++r) S[r] = level[lane + 64 * r];
-                cnt = counters[0];
-                k = counters[1];
-                continue;
-            }
-            ex_fence();
-            const unsigned short e = list[cnt - 1];
-            const int v = e & 0x7fff;
-            --cnt;
-            const int k_next = k - (e >> 15);
-            if (steps >= cap) { go = false; break; }
-            ++steps;
-            ex_clear<R>(S, lane, v);
-            {
-                const unsigned long long* row = P + (size_t)v * words;
-#pragma unroll
-                for (int r = 0; r < R; ++r) C[r] = lane + 64 * r < nw ? S[r] & row[lane + 64 * r] : 0ull;
-            }
-            bool empty = true;
-#pragma unroll
-            for (int r = 0; r < R; ++r) empty = empty && __ballot(C[r] != 0ull) == 0ull;
-            if (empty) {                                             // a maximal clique of d + 2: the first of its size wins
-                if (d + 2 > best && d + 2 <= levels) {
-                    best = d + 2;
-                    found = true;
-                    unsigned short* out = cliques + (size_t)q * levels;
-                    for (int j = lane; j < d; j += 64) out[1 + j] = (unsigned short)path[j];
-                    if (lane == 0) { out[0] = (unsigned short)q; out[d + 1] = (unsigned short)v; }
-                }
-                k = k_next;
-                continue;
-            }
-            if (d + 1 >= levels) { go = false; break; }              // (cannot happen while UB0 bounds the clique number)
-#pragma unroll
-            for (int r = 0; r < R; ++r) level[lane + 64 * r] = S[r];
-            if (lane == 0) { counters[0] = cnt; counters[1] = k_next; path[d] = v; }
-            ++d;
-#pragma unroll
-            for (int r = 0; r < R; ++r) S[r] = C[r];
-            entering = true;
-        }
+        int best;
+        bool go, found;
+        const unsigned steps = ex_subproblem<R>(S, lane, q, lb, nw, words, levels, level_words, cap, P, slice, path,
+                                                cliques + (size_t)q * levels, best, found, go);
         if (lane == 0) { sub_flag[q] = go ? 1 : 2; sub_size[q] = found ? best : 0; sub_steps[q] = steps; }
     }
 }

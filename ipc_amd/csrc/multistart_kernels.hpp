@@ -18,7 +18,8 @@ constexpr int kMsWaves = 4;                             // waves (seeds / rows) 
 constexpr int kMsInfo = 4;                              // info words: n, best size, best position, best candidate (-1: none)
 
 // The live list in processing order (k_set_max's ordered compaction), pos[k] = position of candidate k in it or -1, info[0] = n.
-__global__ __launch_bounds__(1024) void k_ms_live(int N, int words, const int* order, const unsigned long long* bits, int* live,
+// `stride` = words per stored row of the matrix.
+__global__ __launch_bounds__(1024) void k_ms_live(int N, int stride, const int* order, const unsigned long long* bits, int* live,
                                                   int* pos, int* info)
 {
     __shared__ int wcount[16];
@@ -30,7 +31,7 @@ __global__ __launch_bounds__(1024) void k_ms_live(int N, int words, const int* o
     for (int base = 0; base < N; base += 1024) {
         const int p = base + tid;
         const int k = p < N ? order[p] : -1;
-        const bool keep = k >= 0 && ((bits[(size_t)k * words + (k >> 6)] >> (k & 63)) & 1ull);
+        const bool keep = k >= 0 && ((bits[(size_t)k * stride + (k >> 6)] >> (k & 63)) & 1ull);
         const unsigned long long m = __ballot(keep);
         if (lane == 0) wcount[wave] = __popcll(m);
         __syncthreads();
@@ -49,8 +50,9 @@ __global__ __launch_bounds__(1024) void k_ms_live(int N, int words, const int* o
 }
 
 // Row a of P: lane b of trip wb asks for C[l_a][l_{64 wb + b}], the ballot is the word; the words of 64 trips are parked one per
-// lane and leave in one coalesced store.  Words at and beyond ceil(n/64) are never written and never read.
-__global__ __launch_bounds__(64 * kMsWaves) void k_ms_compact(int words, const unsigned long long* bits, const int* live,
+// lane and leave in one coalesced store.  Words at and beyond ceil(n/64) are never written and never read.  `stride` = words per
+// stored row of the input matrix (ipc_set_max_multistart: words; the online matrix: its capacity stride), as in k_set_max.
+__global__ __launch_bounds__(64 * kMsWaves) void k_ms_compact(int words, int stride, const unsigned long long* bits, const int* live,
                                                               const int* info, unsigned long long* P)
 {
     const int lane = threadIdx.x & 63;
@@ -58,7 +60,7 @@ __global__ __launch_bounds__(64 * kMsWaves) void k_ms_compact(int words, const u
     const int n = info[0];
     if (a >= n) return;
     const int nw = (n + 63) >> 6;
-    const unsigned long long* row = bits + (size_t)live[a] * words;
+    const unsigned long long* row = bits + (size_t)live[a] * stride;
     unsigned long long* out = P + (size_t)a * words;
     unsigned long long mine = 0ull;
     for (int wb = 0; wb < nw; ++wb) {

@@ -68,6 +68,11 @@ class EngineBackend:
         """The exact set or its bracket (ipc_set_max_exact): accepted [N] uint8; blocks the host, returns the report dict."""
         return self.e.set_max_exact(bits.data_ptr(), accepted.data_ptr(), self._stream())
 
+    def set_max_exact_resume(self, bits, first, accepted):
+        """The exact set resumed from `accepted`, a maximum set of the candidates < first (ipc_set_max_exact_resume): accepted
+        [N] uint8, in and out; blocks the host, returns the report dict."""
+        return self.e.set_max_exact_resume(bits.data_ptr(), first, accepted.data_ptr(), self._stream())
+
 
 class ShardedMatrix:
     def __init__(self, backend, rank=0, world=1, group=None, force_gather=False):
