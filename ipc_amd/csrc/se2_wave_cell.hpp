@@ -19,7 +19,8 @@
 //     free, and a slot's constants sit at compile-time offsets from one per-lane address.
 //   * trial poses / trial errors are not stored: a trial is one sweep that steps, evaluates and
 //     sums chi2 on the fly; an accepted trial is re-swept once to commit.  For M > 8 the committed
-//     errors are not stored either (recomputed where used).
+//     errors are not stored across iterations either: each iteration recomputes them (M = 9, 11: once, in phase A,
+//     and parks them in accumulator registers for phases B1 and C; M = 13: in each of the three phases).
 //   * with one wave per SIMD every instruction costs issue time: the per-slot code is pinned in
 //     place (IPC_PIN*), loop end points are found by one bit test per slot, constants are fetched
 //     one slot ahead where registers allow.
@@ -161,21 +162,60 @@ template <int V> struct IntC { static constexpr int value = V; };
 #define IPC_PIN2(a, b) asm volatile("" : "+v"(a), "+v"(b) : : "memory")
 #define IPC_PIN3(a, b, c) asm volatile("" : "+v"(a), "+v"(b), "+v"(c) : : "memory")
 
-// KEEP_E: the odometry errors of the committed state live in registers (3 doubles per pose).  For
-// large M they are recomputed from the poses where needed (three times per iteration, ~20 flops
-// each) to stay inside the register file; a commit is then a pure pose update.
+// KEEP_E: the odometry errors of the committed state live in registers (3 doubles per pose), written by the commit
+// sweep.  For large M they are recomputed from the poses where needed (~20 flops each) to stay inside the register
+// file; a commit is then a pure pose update.
 #ifndef IPC_KEEPE_MAX
 #define IPC_KEEPE_MAX 8
 #endif
+// Look-ahead of the slot constants (PF below) up to this M; the one-wave kernels have room for it one step further.
 #ifndef IPC_PF_MAX
 #define IPC_PF_MAX 9
 #endif
-template <int M, int NL, bool STAGED, int W = 1, bool KEEP_E = (M <= IPC_KEEPE_MAX)>
+#ifndef IPC_PF_MAX_W1                                  // (a smaller IPC_PF_MAX, as -DIPC_PF_MAX=0, holds for them too)
+#define IPC_PF_MAX_W1 (IPC_PF_MAX < 9 ? IPC_PF_MAX : 11)
+#endif
+// PARK_E (M = 9 and 11): phase A recomputes the errors as before and parks them in accumulator registers, by hand;
+// phases B1 and C of the same iteration read them back instead of recomputing (the committed poses do not move in
+// between), and no longer load the measurement translation and angle.  These kernels fill the vector registers: left
+// to the register allocator, 6 M more live values come back as several hundred accumulator copies per dog-leg
+// iteration, more than two recomputations cost.  Parked explicitly, a slot's three doubles cost six copies in phase A
+// and six in each of B1 and C; nothing stays parked across the trial loop, and a commit remains a pure pose update
+// (no neighbour exchange, no constants).  The parked value IS what err_of recomputes there: same bits.
+// -DIPC_PARKE_SET=0 switches it off (bit i of the set: M = i).  M = 13 recomputes.
+#ifndef IPC_PARKE_SET
+#define IPC_PARKE_SET ((1 << 9) | (1 << 11))
+#endif
+// how se2_wave_solve holds the committed errors: 0 recomputed, 1 in vector registers (KEEP_E), 2 parked by phase A
+template <int M>
+constexpr int se2_err_store() { return M <= IPC_KEEPE_MAX ? 1 : (((IPC_PARKE_SET >> M) & 1) ? 2 : 0); }
+
+struct ParkedE { int w[6]; };                        // three doubles as six accumulator registers
+__device__ __forceinline__ void park_e(ParkedE& p, double e0, double e1, double e2)
+{
+    asm volatile("v_accvgpr_write_b32 %0, %6\n\tv_accvgpr_write_b32 %1, %7\n\tv_accvgpr_write_b32 %2, %8\n\t"
+                 "v_accvgpr_write_b32 %3, %9\n\tv_accvgpr_write_b32 %4, %10\n\tv_accvgpr_write_b32 %5, %11"
+                 : "=a"(p.w[0]), "=a"(p.w[1]), "=a"(p.w[2]), "=a"(p.w[3]), "=a"(p.w[4]), "=a"(p.w[5])
+                 : "v"(__double2loint(e0)), "v"(__double2hiint(e0)), "v"(__double2loint(e1)), "v"(__double2hiint(e1)),
+                   "v"(__double2loint(e2)), "v"(__double2hiint(e2)));
+}
+__device__ __forceinline__ void unpark_e(const ParkedE& p, double& e0, double& e1, double& e2)
+{
+    int l0, h0, l1, h1, l2, h2;
+    asm volatile("v_accvgpr_read_b32 %0, %6\n\tv_accvgpr_read_b32 %1, %7\n\tv_accvgpr_read_b32 %2, %8\n\t"
+                 "v_accvgpr_read_b32 %3, %9\n\tv_accvgpr_read_b32 %4, %10\n\tv_accvgpr_read_b32 %5, %11"
+                 : "=v"(l0), "=v"(h0), "=v"(l1), "=v"(h1), "=v"(l2), "=v"(h2)
+                 : "a"(p.w[0]), "a"(p.w[1]), "a"(p.w[2]), "a"(p.w[3]), "a"(p.w[4]), "a"(p.w[5]));
+    e0 = __hiloint2double(h0, l0); e1 = __hiloint2double(h1, l1); e2 = __hiloint2double(h2, l2);
+}
+
+template <int M, int NL, bool STAGED, int W = 1, int E_STORE = se2_err_store<M>()>
 __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int L, const int (&cand)[2], int iterations,
                                WaveScratch<NL>& sh, const double* cst, int wlo, int wstride, CellResult& res,
                                PairBox* box = nullptr, int seq0 = 0, int* seq_out = nullptr)
 {
     static_assert(W == 1 || W == 2 || W == 4, "one, two or four cooperating waves per cell");
+    constexpr bool KEEP_E = E_STORE == 1, PARK_E = E_STORE == 2;
     constexpr int NS = NL * 3;
     const double term_scale = P.term_eps / (double)(L + NL);   // 0: the test is off
     bool lastGN = false;
@@ -302,6 +342,7 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
     // ---------------- per-lane state ----------------
     Pose2 X[M];
     double ex[KEEP_E ? M : 1], ey[KEEP_E ? M : 1], eth[KEEP_E ? M : 1];
+    ParkedE pe[PARK_E ? M : 1];                      // (phase A writes them before phases B1 and C read them)
     double bx[M], by[M], bth[M];
     double hx[M], hy[M], hth[M];
     Pose2 gauge;
@@ -399,8 +440,9 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
         if (WANT & 8) c.sg = ldsym(F_SG, s);
     };
     constexpr int kErrWant = KEEP_E ? 0 : 3;         // what err_of needs when the errors are recomputed
+    constexpr int kErrWantBC = (KEEP_E || PARK_E) ? 0 : 3;   // ... in phases B1 and C, which read what phase A parked
     // the look-ahead costs one SlotConst of registers: only where the register file has room
-    constexpr bool PF = M <= IPC_PF_MAX;
+    constexpr bool PF = M <= (W == 1 ? IPC_PF_MAX_W1 : IPC_PF_MAX);
 
     // pose j-1 of slot 0: slot M-1 of the lane below (lane 0 of the cell: the gauge; lane 0 of the
     // pair's second wave: lane 63 of the first, through the mailbox)
@@ -486,6 +528,11 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
         if (KEEP_E) { e0 = ex[s]; e1 = ey[s]; e2 = eth[s]; return; }
         se2_error(a, X[s], K.tzx, K.tzy, K.cz, K.sz, K.thz, e0, e1, e2);
         if (!(j0 + s <= L)) { e0 = 0.0; e1 = 0.0; e2 = 0.0; }
+    };
+    // the same in phases B1 and C: parked by phase A of this iteration (the committed poses have not moved since)
+    auto err_again = [&](int s, const Pose2& a, const SlotConst& K, double& e0, double& e1, double& e2) {
+        if (PARK_E) unpark_e(pe[s], e0, e1, e2);
+        else err_of(s, a, K, e0, e1, e2);
     };
     // gn (wave-uniform): the step is exactly h (Gauss-Newton trial, p = 0, q = 1): X + (0 b + 1 h) and
     // X + h are the same bits, so the b operands and two operations per component are skipped.
@@ -600,6 +647,7 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
             const double cP = a.c * cz - a.s * sz, sP = a.s * cz + a.c * sz;
             double e0, e1, e2, qx, qy, qth;
             err_of(s, a, K, e0, e1, e2);                                // zero on idle slots
+            if (PARK_E) park_e(pe[s], e0, e1, e2);
             K.om.mul(e0, e1, e2, qx, qy, qth);
             gx = cP * qx - sP * qy;
             gy = sP * qx + cP * qy;
@@ -681,7 +729,7 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
             v1[0] = bbp;
             double qbx, qby, qbth;
             prev3(bx[M - 1], by[M - 1], bth[M - 1], qbx, qby, qbth);
-            constexpr int kWantB = 2 | 4 | 8 | kErrWant;
+            constexpr int kWantB = 2 | 4 | 8 | kErrWantBC;
             SlotConst Kn;
             if (PF) ld_slot(0, Kn, IntC<kWantB>{});
 #pragma unroll
@@ -713,7 +761,7 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
                 psi[3] = C11 - ky * c1 - ky * psi[4];
                 psi[5] = sth;
                 double e0, e1, e2;
-                err_of(s, a, K, e0, e1, e2);
+                err_again(s, a, K, e0, e1, e2);
                 const double w0 = c * e0 - sn * e1 - kx * e2;
                 const double w1 = sn * e0 + c * e1 - ky * e2;
                 const double w2 = e2;
@@ -906,7 +954,7 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
         {
             // rho into (hx, hy, hth); theta prefix in-lane
             double run = 0.0;
-            constexpr int kWantC = 2 | 8 | kErrWant;
+            constexpr int kWantC = 2 | 8 | kErrWantBC;
             SlotConst Kn;
             if (PF) ld_slot(0, Kn, IntC<kWantC>{});
 #pragma unroll
@@ -930,7 +978,7 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
                 double vx, vy, vth;
                 K.sg.mul(wx, wy, wth, vx, vy, vth);
                 double e0, e1, e2;
-                err_of(s, a, K, e0, e1, e2);
+                err_again(s, a, K, e0, e1, e2);
                 const double ux = -vx - e0, uy = -vy - e1, uth = -vth - e2;
                 hx[s] = v ? c * ux - sn * uy : 0.0;
                 hy[s] = v ? sn * ux + c * uy : 0.0;
