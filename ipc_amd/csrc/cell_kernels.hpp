@@ -1,5 +1,5 @@
 // Launch interface of the cell-solver kernels.  The kernels are heavily templated, so they live
-// in their own translation units (se2_block.hip, se2_wave.hip, se2_pair.hip, se2_quad.hip, se3_block.hip) that are compiled
+// in their own translation units (se2_block.hip, se2_wave.hip, se2_wave_kt.hip, se2_pair.hip, se2_pair_kt.hip, se2_quad.hip, se3_block.hip) that are compiled
 // in parallel and linked into libipc_amd.so; engine.hip only sees these prototypes.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -80,5 +80,19 @@ constexpr int kNumQuadM = sizeof(kQuadM) / sizeof(kQuadM[0]);
 constexpr int kQuadVariantBase = 300;
 hipError_t launch_se2_quad(int nl, int M, int n, hipStream_t st, const Se2View& P, const int2* cells,
                            SolveParams prm, CellOut out, unsigned* counter, int n_cu);
+
+// ---- kept-trial wave and pair kernels (SE2, se2_wave_kt.hip / se2_pair_kt.hip): the same cells, capacities and
+// results as the wave / pair kernel of the same M; an accepted trial is committed from the poses its sweep parked in
+// accumulator registers instead of by a second sweep (KEEP_TRIAL of se2_wave_solve).  Policy tokens "kwM" / "kpM" ----
+static const int kWaveKtM[] = {5, 7, 9, 11};
+constexpr int kNumWaveKtM = sizeof(kWaveKtM) / sizeof(kWaveKtM[0]);
+constexpr int kWaveKtVariantBase = 500;
+hipError_t launch_se2_wave_kt(int nl, int M, int n, hipStream_t st, const Se2View& P, const int2* cells,
+                              SolveParams prm, CellOut out, unsigned* counter, int n_cu);
+static const int kPairKtM[] = {7, 9, 11};
+constexpr int kNumPairKtM = sizeof(kPairKtM) / sizeof(kPairKtM[0]);
+constexpr int kPairKtVariantBase = 600;
+hipError_t launch_se2_pair_kt(int nl, int M, int n, hipStream_t st, const Se2View& P, const int2* cells,
+                              SolveParams prm, CellOut out, unsigned* counter, int n_cu);
 
 }  // namespace ipc

@@ -596,8 +596,9 @@ __global__ __launch_bounds__(1024) void k_set_max(int N, int words, int stride, 
 // Chain-length bins: each bin is served by one (W, M) kernel variant.  The policy string
 // (env IPC_SE2_POLICY, default below) lists the variants to use as "WxM" tokens (block kernel, W
 // waves per cell, M poses per lane), "wM" tokens (SE2 wave kernel, one wave per cell, M poses per
-// lane), "pM" tokens (SE2 pair kernel, two waves per cell) or "qM" tokens (SE2 quad kernel, four
-// waves per cell); a cell goes to the listed variant of
+// lane), "pM" tokens (SE2 pair kernel, two waves per cell), "qM" tokens (SE2 quad kernel, four
+// waves per cell) or "kwM" / "kpM" tokens (the kept-trial form of the wave / pair kernel, same capacity and
+// results: DESIGN.md 4.1); a cell goes to the listed variant of
 // smallest capacity 64*W*M that holds it.
 struct BinPlan {
     BinCaps caps;
@@ -607,7 +608,9 @@ struct BinPlan {
     int latency_variant[kMaxBins];
     int latency_below[kMaxBins];
 };
-static const char* kDefaultPolicy = "w1,w3,w5,w7,w9,w11,w13,p7,p9,p11,q7,q9,q11,q13,16x4,16x8,16x16";
+// kwM / kpM where the kept-trial kernel passed its static and its measured gate: not at M = 11, whose
+// kept-trial kernels spill to scratch and run slower than w11 / p11
+static const char* kDefaultPolicy = "w1,w3,kw5,kw7,kw9,w11,w13,kp7,kp9,p11,q7,q9,q11,q13,16x4,16x8,16x16";
 // engine streams + the caller's stream = the runtime's four hardware queues for SE2; the long SE3
 // launches gain a little from a fourth engine stream
 static const int kDefaultSideStreams2 = 7, kDefaultSideStreams3 = 7;      // (round 5: 2 / 3 until the side streams came from the process pool -- at 8 ranks a shard's bins hold fewer cells than the GPU has CUs and only concurrent launches fill it: C2 emulated 6.53x -> 7.07x, one rank unchanged)
@@ -630,7 +633,13 @@ static bool make_plan(BinPlan& bp, int dim, std::string& err)
         int w = 0, m = 0;
         const std::string tok = pol.substr(pos, e - pos);
         int v = -1;
-        if (dim == 2 && sscanf(tok.c_str(), "w%d", &m) == 1) {          // wave kernel, M poses per lane
+        if (dim == 2 && sscanf(tok.c_str(), "kw%d", &m) == 1) {         // kept-trial wave kernel (before "w%d": a prefix, not a suffix, names it)
+            w = 1;
+            for (int k = 0; k < kNumWaveKtM; ++k) if (kWaveKtM[k] == m) v = kWaveKtVariantBase + m;
+        } else if (dim == 2 && sscanf(tok.c_str(), "kp%d", &m) == 1) {  // kept-trial pair kernel
+            w = 2;
+            for (int k = 0; k < kNumPairKtM; ++k) if (kPairKtM[k] == m) v = kPairKtVariantBase + m;
+        } else if (dim == 2 && sscanf(tok.c_str(), "w%d", &m) == 1) {   // wave kernel, M poses per lane
             w = 1;
             for (int k = 0; k < kNumWaveM; ++k) if (kWaveM[k] == m) v = kWaveVariantBase + m;
         } else if (dim == 2 && sscanf(tok.c_str(), "p%d", &m) == 1) {   // pair kernel, two waves per cell
@@ -1919,7 +1928,9 @@ struct SlotLauncher {
         int var = h->plan.variant[b];
         if (h->plan.latency_variant[b] >= 0 && n < h->plan.latency_below[b] * h->n_cu) var = h->plan.latency_variant[b];
         if (h->dim == 2)
-            return var >= kQuadVariantBase   ? launch_se2_quad(nl, var - kQuadVariantBase, n, ls, P, cells, sp, out, ctr, h->n_cu)
+            return var >= kPairKtVariantBase ? launch_se2_pair_kt(nl, var - kPairKtVariantBase, n, ls, P, cells, sp, out, ctr, h->n_cu)
+                   : var >= kWaveKtVariantBase ? launch_se2_wave_kt(nl, var - kWaveKtVariantBase, n, ls, P, cells, sp, out, ctr, h->n_cu)
+                   : var >= kQuadVariantBase ? launch_se2_quad(nl, var - kQuadVariantBase, n, ls, P, cells, sp, out, ctr, h->n_cu)
                    : var >= kPairVariantBase ? launch_se2_pair(nl, var - kPairVariantBase, n, ls, P, cells, sp, out, ctr, h->n_cu)
                    : var >= kWaveVariantBase ? launch_se2_wave(nl, var - kWaveVariantBase, n, ls, P, cells, sp, out, ctr, h->n_cu)
                                              : launch_se2_block(nl, var, n, ls, P, cells, sp, out);

@@ -13,72 +13,28 @@ constexpr int kWavesPerGroup = 4;
 #endif
 constexpr int kLdsBudget = IPC_LDS_BUDGET;
 
-// The four waves of a workgroup form 4 / W teams, each team solves one cell together (wave w of the
-// team owns poses 64 M w + 1 .. 64 M (w + 1)); the teams are independent and share the staged chain
-// constants.
-template <int W, int M, int NL, bool STAGED>
-__global__ __launch_bounds__(64 * kWavesPerGroup, 1) void se2_group_kernel(Se2View P, const int2* cells, int ncells,
-                                                                           unsigned* counter, SolveParams prm,
-                                                                           CellOut out, int wlo, int wlen, int wstride)
+// Two kernel templates, one text (se2_group_kernel_def.hpp): se2_group_kernel re-sweeps an accepted trial to commit it;
+// se2_group_kernel_kt (kept trial) reads it back from the accumulator registers where the trial sweep parked it.
+#define IPC_GROUP_KERNEL_NAME se2_group_kernel
+#define IPC_GROUP_KEEP_TRIAL false
+#include "se2_group_kernel_def.hpp"
+#undef IPC_GROUP_KERNEL_NAME
+#undef IPC_GROUP_KEEP_TRIAL
+#define IPC_GROUP_KERNEL_NAME se2_group_kernel_kt
+#define IPC_GROUP_KEEP_TRIAL true
+#include "se2_group_kernel_def.hpp"
+#undef IPC_GROUP_KERNEL_NAME
+#undef IPC_GROUP_KEEP_TRIAL
+
+// (only the chosen template is instantiated: a translation unit emits the kernels it launches and no others)
+template <int W, int M, int NL, bool STAGED, bool KEEP_TRIAL>
+constexpr auto se2_group_kernel_of()
 {
-    extern __shared__ double dyn_lds[];
-    constexpr int kPairs = kWavesPerGroup / W;
-    constexpr int kScratchDoubles = (sizeof(WaveScratch<NL>) + 7) / 8;
-    constexpr int kBoxDoubles = (sizeof(PairBox) + 7) / 8;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, pair = wave / W, wsub = wave & (W - 1);
-    WaveScratch<NL>& sh = *reinterpret_cast<WaveScratch<NL>*>(dyn_lds + pair * kScratchDoubles);
-    PairBox* box = reinterpret_cast<PairBox*>(dyn_lds + kPairs * kScratchDoubles + pair * kBoxDoubles);
-    double* cst = dyn_lds + kPairs * (kScratchDoubles + kBoxDoubles);
-    if (STAGED) {
-        for (int f = 0; f < (int)F_SG; ++f)
-            for (int i = threadIdx.x; i < wstride; i += 64 * kWavesPerGroup)
-                cst[i * (int)F_SG + f] = i < wlen ? P.chain[(size_t)f * P.estride + wlo + i] : 0.0;
-    }
-    if (lane == 0) box->flag[wsub] = 0;
-    __syncthreads();
-    int seq = 0;
-    for (;;) {
-        // the team's first wave takes a cell from the queue and tells the others
-        ++seq;
-        unsigned c = 0;
-        if (wsub == 0 && lane == 0) {
-            c = atomicAdd(counter, 1u);
-            mb_store(&box->data[0][seq & 1][0], (double)c);
-        }
-        wave_sync();
-        if (lane == 0) __hip_atomic_store(&box->flag[wsub], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-#pragma unroll
-        for (int o = 0; o < W; ++o) {
-            if (o == wsub) continue;
-            while (__hip_atomic_load(&box->flag[o], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) - seq < 0)
-                IPC_SPIN_WAIT();
-        }
-        wave_sync();
-        c = (unsigned)mb_load(&box->data[0][seq & 1][0]);
-        c = (unsigned)__builtin_amdgcn_readfirstlane((int)c);
-        if (c >= (unsigned)ncells) break;
-        const int2 cc = cells[c];
-        int cand[2] = {cc.x, cc.y};
-        int lo = min(P.cand_from[cc.x], P.cand_to[cc.x]), hi = max(P.cand_from[cc.x], P.cand_to[cc.x]);
-        if (NL == 2) {
-            lo = min(lo, min(P.cand_from[cc.y], P.cand_to[cc.y]));
-            hi = max(hi, max(P.cand_from[cc.y], P.cand_to[cc.y]));
-        }
-        const int L = hi - lo;
-        const int base = NL == 1 ? prm.fast_iter : prm.slow_iter;
-        const int iterations = (L + NL > 100) ? base * 5 : base;       // consensus_utils.cpp:12-13
-        CellResult r;
-        se2_wave_solve<M, NL, STAGED, W>(P, lo, L, cand, iterations, sh, cst, wlo, wstride, r, box, seq, &seq);
-        if (wsub == 0 && lane == 0) {
-            out.max_chi2[c] = r.max_chi2;
-            out.chi2_total[c] = r.chi2_total;
-            out.meta[c] = make_int4(r.iterations, r.tries, r.flags, r.evals);
-        }
-        wave_sync();
-    }
+    if constexpr (KEEP_TRIAL) return &se2_group_kernel_kt<W, M, NL, STAGED>;
+    else return &se2_group_kernel<W, M, NL, STAGED>;
 }
 
-template <int W, int M, int NL>
+template <int W, int M, int NL, bool KEEP_TRIAL = false>
 static hipError_t launch_group(int n, hipStream_t st, const Se2View& P, const int2* cells, SolveParams prm, CellOut out,
                               unsigned* counter, int n_cu)
 {
@@ -89,12 +45,12 @@ static hipError_t launch_group(int n, hipStream_t st, const Se2View& P, const in
     const size_t staged = scratch + sizeof(double) * (size_t)F_SG * wstride;
     const int groups = std::max(1, std::min(n_cu, (n + kPairs - 1) / kPairs));
     if (staged <= (size_t)kLdsBudget) {
-        auto k = se2_group_kernel<W, M, NL, true>;
+        auto k = se2_group_kernel_of<W, M, NL, true, KEEP_TRIAL>();
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)staged);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k, dim3(groups), dim3(64 * kWavesPerGroup), staged, st, P, cells, n, counter, prm, out, 0, E, wstride);
     } else {
-        auto k = se2_group_kernel<W, M, NL, false>;
+        auto k = se2_group_kernel_of<W, M, NL, false, KEEP_TRIAL>();
         hipLaunchKernelGGL(k, dim3(groups), dim3(64 * kWavesPerGroup), scratch, st, P, cells, n, counter, prm, out, 0, E, wstride);
     }
     return hipGetLastError();

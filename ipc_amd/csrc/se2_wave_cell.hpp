@@ -17,8 +17,10 @@
 //     are staged ONCE per workgroup for the whole window of the launch, one record per edge, and
 //     shared by every cell it solves; M is odd so the lane stride of M records is bank-conflict
 //     free, and a slot's constants sit at compile-time offsets from one per-lane address.
-//   * trial poses / trial errors are not stored: a trial is one sweep that steps, evaluates and
-//     sums chi2 on the fly; an accepted trial is re-swept once to commit.  For M > 8 the committed
+//   * trial poses / trial errors are not stored in vector registers: a trial is one sweep that steps, evaluates and
+//     sums chi2 on the fly.  An accepted trial is re-swept once to commit (same coefficients, same bits), or, in the
+//     kept-trial variants (KEEP_TRIAL, the se2_*_kernel_kt kernels), read back from the accumulator registers where
+//     the trial sweep parked its poses (and, for M <= 8, its errors) by hand.  For M > 8 the committed
 //     errors are not stored across iterations either: each iteration recomputes them (M = 9, 11: once, in phase A,
 //     and parks them in accumulator registers for phases B1 and C; M = 13: in each of the three phases).
 //   * with one wave per SIMD every instruction costs issue time: the per-slot code is pinned in
@@ -209,7 +211,41 @@ __device__ __forceinline__ void unpark_e(const ParkedE& p, double& e0, double& e
     e0 = __hiloint2double(h0, l0); e1 = __hiloint2double(h1, l1); e2 = __hiloint2double(h2, l2);
 }
 
-template <int M, int NL, bool STAGED, int W = 1, int E_STORE = se2_err_store<M>()>
+// KEEP_TRIAL: every trial sweep parks the pose it forms in each slot (x, y, theta, cos, sin: ten accumulator registers),
+// and where the errors are kept (KEEP_E) the slot's three error values as a commit would store them.  An accepted trial
+// is then committed by reading these back: no second sweep, so no stepping, no angle wrap, no rotation or sincos, and
+// for KEEP_E no se2_error, no constants and no neighbour exchange (both waves of a pair skip it together, so their
+// sequence numbers stay in step).  A rejected trial leaves X untouched and the next trial overwrites what was parked.
+// The registers are those that pe (PARK_E) leaves dead during the trial loop plus the free accumulator registers; no
+// vector register lives longer.  The parked values ARE what the commit sweep recomputes: same bits.
+struct ParkedPose { int w[10]; };                    // x, y, theta, cos, sin as ten accumulator registers
+__device__ __forceinline__ void park_pose(ParkedPose& p, const Pose2& Y)
+{
+    asm volatile("v_accvgpr_write_b32 %0, %10\n\tv_accvgpr_write_b32 %1, %11\n\tv_accvgpr_write_b32 %2, %12\n\t"
+                 "v_accvgpr_write_b32 %3, %13\n\tv_accvgpr_write_b32 %4, %14\n\tv_accvgpr_write_b32 %5, %15\n\t"
+                 "v_accvgpr_write_b32 %6, %16\n\tv_accvgpr_write_b32 %7, %17\n\tv_accvgpr_write_b32 %8, %18\n\t"
+                 "v_accvgpr_write_b32 %9, %19"
+                 : "=a"(p.w[0]), "=a"(p.w[1]), "=a"(p.w[2]), "=a"(p.w[3]), "=a"(p.w[4]), "=a"(p.w[5]), "=a"(p.w[6]),
+                   "=a"(p.w[7]), "=a"(p.w[8]), "=a"(p.w[9])
+                 : "v"(__double2loint(Y.x)), "v"(__double2hiint(Y.x)), "v"(__double2loint(Y.y)), "v"(__double2hiint(Y.y)),
+                   "v"(__double2loint(Y.th)), "v"(__double2hiint(Y.th)), "v"(__double2loint(Y.c)), "v"(__double2hiint(Y.c)),
+                   "v"(__double2loint(Y.s)), "v"(__double2hiint(Y.s)));
+}
+__device__ __forceinline__ void unpark_pose(const ParkedPose& p, Pose2& Y)
+{
+    int l0, h0, l1, h1, l2, h2, l3, h3, l4, h4;
+    asm volatile("v_accvgpr_read_b32 %0, %10\n\tv_accvgpr_read_b32 %1, %11\n\tv_accvgpr_read_b32 %2, %12\n\t"
+                 "v_accvgpr_read_b32 %3, %13\n\tv_accvgpr_read_b32 %4, %14\n\tv_accvgpr_read_b32 %5, %15\n\t"
+                 "v_accvgpr_read_b32 %6, %16\n\tv_accvgpr_read_b32 %7, %17\n\tv_accvgpr_read_b32 %8, %18\n\t"
+                 "v_accvgpr_read_b32 %9, %19"
+                 : "=v"(l0), "=v"(h0), "=v"(l1), "=v"(h1), "=v"(l2), "=v"(h2), "=v"(l3), "=v"(h3), "=v"(l4), "=v"(h4)
+                 : "a"(p.w[0]), "a"(p.w[1]), "a"(p.w[2]), "a"(p.w[3]), "a"(p.w[4]), "a"(p.w[5]), "a"(p.w[6]), "a"(p.w[7]),
+                   "a"(p.w[8]), "a"(p.w[9]));
+    Y.x = __hiloint2double(h0, l0); Y.y = __hiloint2double(h1, l1); Y.th = __hiloint2double(h2, l2);
+    Y.c = __hiloint2double(h3, l3); Y.s = __hiloint2double(h4, l4);
+}
+
+template <int M, int NL, bool STAGED, int W = 1, int E_STORE = se2_err_store<M>(), bool KEEP_TRIAL = false>
 __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int L, const int (&cand)[2], int iterations,
                                WaveScratch<NL>& sh, const double* cst, int wlo, int wstride, CellResult& res,
                                PairBox* box = nullptr, int seq0 = 0, int* seq_out = nullptr)
@@ -343,6 +379,8 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
     Pose2 X[M];
     double ex[KEEP_E ? M : 1], ey[KEEP_E ? M : 1], eth[KEEP_E ? M : 1];
     ParkedE pe[PARK_E ? M : 1];                      // (phase A writes them before phases B1 and C read them)
+    ParkedPose tY[KEEP_TRIAL ? M : 1];               // (a trial sweep writes them before an accepted trial reads them)
+    ParkedE tE[(KEEP_TRIAL && KEEP_E) ? M : 1];
     double bx[M], by[M], bth[M];
     double hx[M], hy[M], hth[M];
     Pose2 gauge;
@@ -579,6 +617,10 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
                 part += v ? c2 : 0.0;
             }
             if (MODE != 1 && KEEP_E) { ex[s] = v ? e0 : 0.0; ey[s] = v ? e1 : 0.0; eth[s] = v ? e2 : 0.0; }
+            if constexpr (MODE == 1 && KEEP_TRIAL) {
+                park_pose(tY[s], Y);
+                if constexpr (KEEP_E) park_e(tE[s], v ? e0 : 0.0, v ? e1 : 0.0, v ? e2 : 0.0);
+            }
             if (MODE != 2 && ((ownSlots >> s) & 1u)) {
 #pragma unroll
                 for (int l = 0; l < NL; ++l) {
@@ -1095,7 +1137,19 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
                 currentChi = newChi;
                 cur = trial;
                 IPC_WTICK(tmT)
-                sweep(IntC<2>{}, anyBig, pcoef, qcoef, trial, stepType == 0, false);
+                if constexpr (KEEP_TRIAL) {
+#pragma unroll
+                    for (int s = 0; s < M; ++s) {
+                        unpark_pose(tY[s], X[s]);
+                        // Pinned as the commit sweep pins what it writes, in the pair kernels only: there it keeps a value that
+                        // lives across the whole solve (gauge.x) in its vector register in kp9, in the one-wave kernels the
+                        // same pin moves two more such values of kw9 to accumulator registers.
+                        if constexpr (W > 1) IPC_PIN3(X[s].x, X[s].y, X[s].th);
+                        if constexpr (KEEP_E) unpark_e(tE[s], ex[s], ey[s], eth[s]);
+                    }
+                } else {
+                    sweep(IntC<2>{}, anyBig, pcoef, qcoef, trial, stepType == 0, false);
+                }
                 IPC_WTICK(tmK)
             }
             if (rho_gt(0.75)) delta = fmax(delta, 3 * hdlNorm);

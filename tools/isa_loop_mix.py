@@ -86,7 +86,15 @@ def _demangle(names):
 
 
 def short_name(demangled):
-    """se2_wave_kernel<9, 2, true> -> w9/nl2/staged; se2_group_kernel<2, 9, 2, true> -> p9/nl2/staged (W = 4: q)."""
+    """se2_wave_kernel<9, 2, true> -> w9/nl2/staged; se2_group_kernel<2, 9, 2, true> -> p9/nl2/staged (W = 4: q);
+    the kept-trial kernels se2_wave_kernel_kt / se2_group_kernel_kt -> kw9/..., kp9/..."""
+    m = re.search(r"se2_wave_kernel_kt<(\d+), (\d+), (true|false)>", demangled)
+    if m:
+        return "kw%s/nl%s/%s" % (m.group(1), m.group(2), "staged" if m.group(3) == "true" else "unstaged")
+    m = re.search(r"se2_group_kernel_kt<(\d+), (\d+), (\d+), (true|false)>", demangled)
+    if m:
+        return "k%s%s/nl%s/%s" % ({"2": "p", "4": "q"}.get(m.group(1), "g" + m.group(1)), m.group(2), m.group(3),
+                                  "staged" if m.group(4) == "true" else "unstaged")
     m = re.search(r"se2_wave_kernel<(\d+), (\d+), (true|false)>", demangled)
     if m:
         return "w%s/nl%s/%s" % (m.group(1), m.group(2), "staged" if m.group(3) == "true" else "unstaged")
@@ -243,12 +251,19 @@ def parse_report(path):
 
 # ---- the recipe: assembly of the hot instantiations, one per compile (shipped flags, device side only) ----
 def hot_units():
-    """{tag: (translation unit, [-D...])}: w9 w11 w13 of se2_wave.hip, p7 p9 p11 of se2_pair.hip."""
+    """{tag: (translation unit, [-D...])}: w9 w11 w13 of se2_wave.hip, p7 p9 p11 of se2_pair.hip, and the kept-trial
+    kernels kw5 .. kw11 of se2_wave_kt.hip and kp7 kp9 kp11 of se2_pair_kt.hip (with w5 and w7, their counterparts)."""
     u = {}
     for m in (9, 11, 13):
         u["w%d" % m] = ("se2_wave.hip", ["-DIPC_WAVE_ONLY_M=%d" % m])
     for m in (7, 9, 11):
         u["p%d" % m] = ("se2_pair.hip", ["-DIPC_PAIR_ONLY_M=%d" % m])
+    for m in (5, 7):
+        u["w%d" % m] = ("se2_wave.hip", ["-DIPC_WAVE_ONLY_M=%d" % m])
+    for m in (5, 7, 9, 11):
+        u["kw%d" % m] = ("se2_wave_kt.hip", ["-DIPC_WAVE_KT_ONLY_M=%d" % m])
+    for m in (7, 9, 11):
+        u["kp%d" % m] = ("se2_pair_kt.hip", ["-DIPC_PAIR_KT_ONLY_M=%d" % m])
     return u
 
 
