@@ -757,16 +757,18 @@ struct ipc_engine {
     DevBuf<unsigned> d_offsets;
     DevBuf<unsigned> d_wave_ctr;      // work-queue heads of the wave-kernel launches, one per (nl, bin)
     int n_cu = 256;
-    DevBuf<int2> d_cells; size_t cells_cap = 0;
-    DevBuf<double> d_chi, d_chitot; DevBuf<int4> d_meta;
+    // Borderline cells (borderline_band) are solved again with g2o's literal trial loop BY THE CELL KERNELS (term_eps 0)
+    // over compact per-slot lists built on the device (d_lit_*) -- no per-cell copies, no host-driven solves (round 5).
+    struct CellBufs {
+        DevBuf<int2> d_cells, d_lit_cells; DevBuf<double> d_chi, d_chitot, d_lit_chi, d_lit_chitot; DevBuf<int4> d_meta, d_lit_meta;
+        DevBuf<int> d_lit_idx;                         // [cap + 1]: k_slow_flags / k_scan_int write and scan total + 1 entries
+        ScratchCap cap;                                // in cells
+    } cells;
     // The cell lists of (rank, world) change only with the candidates: the two planning passes and their read-back (the
     // first of ipc_solve_rows' two host waits) are paid once per candidate list, not once per step (round 5).
     bool plan_cached = false; int plan_rank = -1, plan_world = 0; size_t plan_total = 0;
     int slow_first_iterations = 96;                    // IPC_SLOW_FIRST (0: off): cells that took this many iterations go to the head of their slot
     std::vector<unsigned> plan_counts, plan_offsets;
-    // Borderline cells (borderline_band) are solved again with g2o's literal trial loop BY THE CELL KERNELS (term_eps 0)
-    // over compact per-slot lists built on the device -- no per-cell copies, no host-driven solves (round 5).
-    DevBuf<int2> d_lit_cells; DevBuf<int> d_lit_idx; DevBuf<double> d_lit_chi, d_lit_chitot; DevBuf<int4> d_lit_meta;
     DevBuf<unsigned> d_slot_off;                       // [slots + 1] first cell of each (loop count, bin) slot
     DevBuf<int> d_recount; PinnedBuf<int> h_recount;      // [slots] borderline cells per slot, then the failed-cell count; pinned copy
     int last_cells = 0, last_long_cells = 0;
@@ -779,7 +781,7 @@ struct ipc_engine {
     hipStream_t side[kMaxSide] = {};
     Event ev_fork, ev_join[kMaxSide], ev_join_own;
     // scratch for ipc_run
-    DevBuf<uint64_t> d_upper, d_bits; DevBuf<unsigned char> d_acc; size_t run_cap = 0;
+    struct RunScratch { DevBuf<uint64_t> d_upper, d_bits; DevBuf<unsigned char> d_acc; ScratchCap cap; } run;   // cap in matrix words; d_acc [N + 64]
     // Online matrix (ipc_run_online): the matrix over the first on_cov candidates stays on the device and an
     // update solves the cells of the columns behind them.  Rows by the identity map, addressed by the capacity stride
     // on_wcap = on_ccap / 64 words (on_ccap a multiple of 64 that doubles), so N crossing a multiple of 64 moves nothing.
@@ -794,46 +796,63 @@ struct ipc_engine {
     // retry's), the literal chi2 with its flag word (sweep_kernels.hpp) and the plan's slot offsets and counts.
     bool sw_valid = false;                             // a first pass of the candidate list of the moment is held
     bool info_from_sweep = false;                      // ipc_cell_info reads the held first pass (the last matrix call was a sweep)
-    size_t sw_total = 0, sw_cap = 0;                   // cells held / capacity of the six arrays below
+    size_t sw_total = 0;                               // cells held
     int sw_long = 0, sw_damped = 0, sw_held = 0;       // long and damped cells of the held pass; literal records held
-    DevBuf<int2> d_sw_cells; DevBuf<double> d_sw_chi, d_sw_chitot, d_sw_lit; DevBuf<int4> d_sw_meta; DevBuf<int> d_sw_flags;
+    struct SweepScratch {
+        DevBuf<int2> d_cells; DevBuf<double> d_chi, d_chitot, d_lit; DevBuf<int4> d_meta; DevBuf<int> d_flags;
+        ScratchCap cap;                                // in cells, of the six arrays above
+        DevBuf<double> d_th; ScratchCap th;            // [fast 0 .. T-1][slow 0 .. T-1] of the call; in pairs
+        // per-chunk scratch: TC upper triangles and matrices ([t][N][words]), accepted bytes and live lists ([t][N])
+        DevBuf<unsigned long long> d_upper, d_bits; DevBuf<unsigned char> d_acc; DevBuf<int> d_live;
+        ScratchCap mat, vec;                           // in words per matrix array / in entries per vector array (vec: a member of mat's group)
+    } sw;
     DevBuf<unsigned> d_sw_slot_off;                    // [slots + 1]
     std::vector<unsigned> sw_counts, sw_offsets;
-    DevBuf<double> d_sw_th; int sw_th_cap = 0;         // [fast 0 .. T-1][slow 0 .. T-1] of the call
-    // per-chunk scratch: TC upper triangles and matrices ([t][N][words]), accepted bytes and live lists ([t][N])
-    DevBuf<unsigned long long> d_sw_upper, d_sw_bits; DevBuf<unsigned char> d_sw_acc; DevBuf<int> d_sw_live;
-    size_t sw_mat_cap = 0, sw_vec_cap = 0;             // capacity in words per matrix array / in entries per vector array
     int sweep_chunk = 0;                               // IPC_SWEEP_CHUNK: cap on the thresholds per chunk (0: none)
     // Monte-Carlo batch (ipc_run_batch): the cells are planned into d_cells & co. like those of any matrix call;
     // what the call holds of its own is the membership words [N][mw] with the 64-bit counter of cells_separate, and the scratch
     // of a chunk of runs: upper triangles and matrices (words), accepted bytes, five int vectors per run (live, lo, hi, order,
     // members), the local-index maps [runs][N] and the descriptors.  One pinned buffer stages every upload.
-    DevBuf<unsigned long long> d_bt_memb, d_bt_sep; size_t bt_memb_cap = 0;
-    DevBuf<unsigned long long> d_bt_upper, d_bt_bits; size_t bt_mat_cap = 0;
-    DevBuf<unsigned char> d_bt_acc; DevBuf<int> d_bt_vec; size_t bt_vec_cap = 0;
-    DevBuf<int> d_bt_loc; size_t bt_loc_cap = 0;
-    DevBuf<BatchRun> d_bt_runs; size_t bt_runs_cap = 0;
-    PinnedBuf<unsigned long long> h_bt_stage; size_t bt_stage_cap = 0;   // in 8-byte words
+    struct BatchScratch {
+        DevBuf<unsigned long long> d_memb, d_sep; ScratchCap memb;
+        DevBuf<unsigned long long> d_upper, d_bits; ScratchCap mat;
+        DevBuf<unsigned char> d_acc; DevBuf<int> d_vec; ScratchCap vec;     // d_vec [5][vec]
+        DevBuf<int> d_loc; ScratchCap loc;
+        DevBuf<BatchRun> d_runs; ScratchCap runs;
+        PinnedBuf<unsigned long long> h_stage; ScratchCap stage;            // in 8-byte words
+    } bt;
     int batch_chunk = 0;                               // IPC_BATCH_CHUNK: cap on the runs per chunk (0: none)
     size_t batch_budget = 0;                           // IPC_BATCH_BUDGET: cap in bytes on a chunk's scratch (0: a quarter of the free memory alone)
     // Multi-start set maximisation (ipc_set_max_multistart): the compact matrix P [N][words] over the live
     // candidates, four int vectors [N] (live list, position map, |S_q| per seed position, ipc_run_multistart's sizes), the
     // info words (multistart_kernels.hpp) and ipc_run_multistart's accepted bytes.
-    DevBuf<unsigned long long> d_ms_P; size_t ms_mat_cap = 0;
-    DevBuf<int> d_ms_vec, d_ms_info; DevBuf<unsigned char> d_ms_acc; int ms_vec_cap = 0;
+    struct MultistartScratch {
+        DevBuf<unsigned long long> d_P; ScratchCap mat;
+        DevBuf<int> d_vec, d_info; DevBuf<unsigned char> d_acc; ScratchCap vec;     // d_vec [4][vec]
+        int* live() const { return vec.part(d_vec, 0); }
+        int* pos() const { return vec.part(d_vec, 1); }
+        int* sz() const { return vec.part(d_vec, 2); }
+        int* sizes() const { return vec.part(d_vec, 3); }
+    } ms;
     int ms_reg_words = 2;                              // IPC_MULTISTART_REG_WORDS: most words of cand a lane keeps in registers (0: always the LDS kernel)
     // Exact maximum consistent set (ipc_set_max_exact), over the multi-start's P: the info words
     // (exact_kernels.hpp), three int vectors [N] (flag, size and steps by subproblem), the depth-first stacks of the wave pool
     // (8-byte words) and the clique of every subproblem (16-bit positions, [n][levels]).
-    DevBuf<int> d_ex_info, d_ex_vec; int ex_vec_cap = 0;
-    DevBuf<unsigned long long> d_ex_ws; size_t ex_ws_cap = 0;
-    DevBuf<unsigned short> d_ex_clq; size_t ex_clq_cap = 0;
-    unsigned ex_step_cap = 1u << 20;                   // IPC_EXACT_STEP_CAP: steps after which a subproblem gives up
     // Resumed exact set (ipc_set_max_exact_resume): the info words and the NEW mask (exact_resume_kernels.hpp),
-    // the root list [N]; flags, sizes, steps, stacks and cliques are those above, by root rank.  ipc_run_online_exact holds its
-    // set in d_on_exact [on_ccap] (sized and moved with the online storage), proven over the first on_ex_cov candidates.
-    DevBuf<int> d_exr_info, d_exr_roots; int exr_roots_cap = 0;
-    DevBuf<unsigned long long> d_exr_new;
+    // the root list [N]; flags, sizes, steps, stacks and cliques are those above, by root rank.
+    struct ExactScratch {
+        DevBuf<int> d_info, d_vec; ScratchCap vec;     // d_vec [3][vec]
+        DevBuf<unsigned long long> d_ws; ScratchCap ws;
+        DevBuf<unsigned short> d_clq; ScratchCap clq;
+        DevBuf<int> d_rinfo, d_roots; ScratchCap roots;     // the resumed search's info words and root list [roots]
+        DevBuf<unsigned long long> d_new;                   // ... and its NEW mask
+        int* flag() const { return vec.part(d_vec, 0); }
+        int* sizes() const { return vec.part(d_vec, 1); }
+        unsigned* steps() const { return (unsigned*)vec.part(d_vec, 2); }
+    } ex;
+    unsigned ex_step_cap = 1u << 20;                   // IPC_EXACT_STEP_CAP: steps after which a subproblem gives up
+    // ipc_run_online_exact holds its set in d_on_exact [on_ccap] (sized and moved with the online storage), proven over the
+    // first on_ex_cov candidates.
     DevBuf<unsigned char> d_on_exact;
     int on_ex_cov = 0, on_ex_proven = 0;
     bool on_ex_resume = true;                          // IPC_ONLINE_EXACT_RESUME=0: every ipc_run_online_exact searches the whole graph (A/B)
@@ -850,7 +869,8 @@ struct ipc_engine {
     bool persist = true;
     bool last_persist = false;                         // which solver holds the poses of the last cluster solve
     DevBuf<int> d_slot; int slot_world = 0; int row_policy = 1;    // row -> shard slot of the last world size (IPC_ROW_BALANCE=cyclic|cost)
-    DevBuf<int> d_failed; int failed_cap = 0; int last_lm_cells = 0;    // cells of the last solve redone with Levenberg damping
+    struct FailedList { DevBuf<int> d_list; ScratchCap cap; } failed;   // [cap + 1] cells to solve again on the host (k_collect_failed)
+    int last_lm_cells = 0;                             // cells of the last solve redone with Levenberg damping
     bool lm_retry = true;                              // IPC_LM_RETRY=0: a failed linear solve ends the optimisation (flags & 2), no damping
     // Cells whose max chi2 ends within this relative distance of their threshold are solved again with g2o's literal
     // trial loop (term_eps 0): the convergence test can move an edge's chi2 by up to 2 sqrt(term_eps) relative,
@@ -1625,7 +1645,7 @@ static int solve_long_cells(ipc_engine* h, hipStream_t st, int nb, const unsigne
         const unsigned n = counts[s];
         if (!n) continue;
         std::vector<int2> cells(n);
-        HIPCHK(hipMemcpy(cells.data(), h->d_cells + offsets[s], sizeof(int2) * n, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(cells.data(), h->cells.d_cells + offsets[s], sizeof(int2) * n, hipMemcpyDeviceToHost));
         std::vector<double> chi(n), tot(n);
         std::vector<int4> meta(n);
         for (unsigned c = 0; c < n; ++c) {
@@ -1641,9 +1661,9 @@ static int solve_long_cells(ipc_engine* h, hipStream_t st, int nb, const unsigne
             meta[c] = make_int4(o.iterations, o.tries, o.flags, o.evals);
         }
         HIPCHK(hipStreamSynchronize(h->own_stream));
-        HIPCHK(hipMemcpy(h->d_chi + offsets[s], chi.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_chitot + offsets[s], tot.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_meta + offsets[s], meta.data(), sizeof(int4) * n, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->cells.d_chi + offsets[s], chi.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->cells.d_chitot + offsets[s], tot.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->cells.d_meta + offsets[s], meta.data(), sizeof(int4) * n, hipMemcpyHostToDevice));
     }
     HIPCHK(hipStreamSynchronize(nullptr));                     // (NULL-stream copies are not ordered against the engine's non-blocking streams: copy_d2d_now)
     return IPC_OK;
@@ -1811,17 +1831,17 @@ static int resolve_failed_cells(ipc_engine* h, int n)
 {
     h->last_lm_cells = 0;
     if (n == 0) return IPC_OK;
-    n = std::min(n, h->failed_cap);
+    n = std::min(n, (int)h->failed.cap.size());
     if (int rc = ensure_incremental(h, "ipc_solve_rows")) return rc;
     std::vector<int> idx(n);
-    HIPCHK(hipMemcpy(idx.data(), h->d_failed, sizeof(int) * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(idx.data(), h->failed.d_list, sizeof(int) * n, hipMemcpyDeviceToHost));
     std::sort(idx.begin(), idx.end());
     for (int q = 0; q < n; ++q) {
         int2 cell;
-        HIPCHK(hipMemcpy(&cell, h->d_cells + idx[q], sizeof(int2), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&cell, h->cells.d_cells + idx[q], sizeof(int2), hipMemcpyDeviceToHost));
         ClusterOut o;
         int4 was;
-        HIPCHK(hipMemcpy(&was, h->d_meta + idx[q], sizeof(int4), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&was, h->cells.d_meta + idx[q], sizeof(int4), hipMemcpyDeviceToHost));
         if (was.z & 2) {
             if (int rc = host_cell_solve(h, cell, true, false, o)) return rc;
             ++h->last_lm_cells;
@@ -1831,9 +1851,9 @@ static int resolve_failed_cells(ipc_engine* h, int n)
             ++h->last_literal_cells;
         }
         const int4 meta = make_int4(o.iterations, o.tries, o.flags, o.evals);
-        HIPCHK(hipMemcpy(h->d_chi + idx[q], &o.max_chi2, sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_chitot + idx[q], &o.chi2_total, sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_meta + idx[q], &meta, sizeof(int4), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->cells.d_chi + idx[q], &o.max_chi2, sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->cells.d_chitot + idx[q], &o.chi2_total, sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->cells.d_meta + idx[q], &meta, sizeof(int4), hipMemcpyHostToDevice));
     }
     HIPCHK(hipStreamSynchronize(nullptr));                     // (NULL-stream copies are not ordered against the engine's non-blocking streams: copy_d2d_now)
     return IPC_OK;
@@ -1872,19 +1892,10 @@ static int plan_cells(ipc_engine* h, hipStream_t st, CellPlan& pl, size_t min_ca
         unsigned o = offsets[s];
         for (int q = 0; q < kPlanSub; ++q) { suboffsets[s * kPlanSub + q] = o; o += subcounts[s * kPlanSub + q]; }
     }
-    if (std::max(total, min_cap) > h->cells_cap) {
+    if (auto& c = h->cells; std::max(total, min_cap) > c.cap.size()) {
         const size_t cap = std::max(total + total / 8 + 1024, min_cap);
-        h->cells_cap = 0;                                // (until all nine are there: a failure part way comes here again)
-        HIPCHK(h->d_cells.alloc(cap));
-        HIPCHK(h->d_chi.alloc(cap));
-        HIPCHK(h->d_chitot.alloc(cap));
-        HIPCHK(h->d_meta.alloc(cap));
-        HIPCHK(h->d_lit_cells.alloc(cap));
-        HIPCHK(h->d_lit_idx.alloc(cap + 1));             // (+ 1: k_slow_flags / k_scan_int write and scan total + 1 entries)
-        HIPCHK(h->d_lit_chi.alloc(cap));
-        HIPCHK(h->d_lit_chitot.alloc(cap));
-        HIPCHK(h->d_lit_meta.alloc(cap));
-        h->cells_cap = cap;
+        HIPCHK(c.cap.grow(cap, sized(c.d_cells, cap), sized(c.d_chi, cap), sized(c.d_chitot, cap), sized(c.d_meta, cap), sized(c.d_lit_cells, cap),
+                          sized(c.d_lit_idx, cap + 1), sized(c.d_lit_chi, cap), sized(c.d_lit_chitot, cap), sized(c.d_lit_meta, cap)));
     }
     if (!h->h_recount) {                                 // (the last of the three)
         HIPCHK(h->d_slot_off.alloc(NS + 1));
@@ -1898,7 +1909,7 @@ static int plan_cells(ipc_engine* h, hipStream_t st, CellPlan& pl, size_t min_ca
     HIPCHK(hipMemcpyAsync(h->d_slot_off, slot_off, sizeof slot_off, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(h->d_offsets, suboffsets, sizeof suboffsets, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(h->d_counters, 0, sizeof(unsigned) * NS * kPlanSub, st));
-    launch_pass(h->d_cells, 1);
+    launch_pass(h->cells.d_cells, 1);
     HIPCHK(hipGetLastError());
     pl.total = total;
     return IPC_OK;
@@ -1983,10 +1994,10 @@ static int solve_first_pass(ipc_engine* h, hipStream_t st, const CellPlan& pl)
         for (int nl = 2; nl >= 1; --nl) {
             const int s = (nl == 1 ? 0 : (kMaxBins + 1)) + b;
             if (!counts[s]) continue;
-            CellOut out{h->d_chi + offsets[s], h->d_chitot + offsets[s], h->d_meta + offsets[s]};
+            CellOut out{h->cells.d_chi + offsets[s], h->cells.d_chitot + offsets[s], h->cells.d_meta + offsets[s]};
             const int lane_q = launches % (n_side + 1);
             hipStream_t ls = lane_q == 0 ? st0 : h->side[lane_q - 1];
-            const hipError_t e = launch_slot(b, nl, (int)counts[s], h->d_cells + offsets[s], out, ls, h->d_wave_ctr + s);
+            const hipError_t e = launch_slot(b, nl, (int)counts[s], h->cells.d_cells + offsets[s], out, ls, h->d_wave_ctr + s);
             if (e != hipSuccess) return fail(IPC_ERR_HIP, "cell kernel launch failed: %s", hipGetErrorString(e));
             ++launches;
         }
@@ -2025,11 +2036,20 @@ static int launch_literal_lists(ipc_engine* h, hipStream_t st, const unsigned* o
             const int s = (nl == 1 ? 0 : (kMaxBins + 1)) + b;
             const int n = h->h_recount[s];
             if (!n) continue;
-            CellOut out{h->d_lit_chi + offsets[s], h->d_lit_chitot + offsets[s], h->d_lit_meta + offsets[s]};
-            const hipError_t e = launch_slot(b, nl, n, h->d_lit_cells + offsets[s], out, st, h->d_wave_ctr + s);
+            CellOut out{h->cells.d_lit_chi + offsets[s], h->cells.d_lit_chitot + offsets[s], h->cells.d_lit_meta + offsets[s]};
+            const hipError_t e = launch_slot(b, nl, n, h->cells.d_lit_cells + offsets[s], out, st, h->d_wave_ctr + s);
             if (e != hipSuccess) return fail(IPC_ERR_HIP, "cell kernel launch failed: %s", hipGetErrorString(e));
         }
     }
+    return IPC_OK;
+}
+
+// room for the cells of a solve of `total` (> 0) cells that go to the host-driven solver
+static int ensure_failed_list(ipc_engine* h, size_t total)
+{
+    if (total <= h->failed.cap.size()) return IPC_OK;
+    const size_t cap = std::max<size_t>(16384, total + total / 8);
+    HIPCHK(h->failed.cap.grow(cap, sized(h->failed.d_list, cap + 1)));
     return IPC_OK;
 }
 
@@ -2043,14 +2063,11 @@ static int solve_collect(ipc_engine* h, hipStream_t st, const CellPlan& pl, doub
         // The cells to solve again: failed linear solves (Levenberg retry by the host-driven solver: degenerate information,
         // rare) and borderline cells (the literal trial loop, by the cell kernels themselves over compact per-slot lists).
         // ONE read-back of the counts -- the single host wait of a repeated step.
-        if (!h->d_failed || (int)total > h->failed_cap) {
-            h->failed_cap = std::max(16384, (int)(total + total / 8));
-            HIPCHK(h->d_failed.alloc((size_t)h->failed_cap + 1));
-        }
+        if (int rc = ensure_failed_list(h, total)) return rc;
         HIPCHK(hipMemsetAsync(h->d_recount, 0, sizeof(int) * (NS + 1), st));
-        hipLaunchKernelGGL(k_collect_failed, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total, (const int4*)h->d_meta,
-                           (const double*)h->d_chi, (const int2*)h->d_cells, h->prm.fast_reject_th, h->prm.slow_reject_th, band,
-                           h->lm_retry, h->failed_cap, h->d_failed, h->d_recount, (const unsigned*)h->d_slot_off, NS, h->d_lit_cells, h->d_lit_idx, nb);
+        hipLaunchKernelGGL(k_collect_failed, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total, (const int4*)h->cells.d_meta,
+                           (const double*)h->cells.d_chi, (const int2*)h->cells.d_cells, h->prm.fast_reject_th, h->prm.slow_reject_th, band,
+                           h->lm_retry, (int)h->failed.cap.size(), h->failed.d_list, h->d_recount, (const unsigned*)h->d_slot_off, NS, h->cells.d_lit_cells, h->cells.d_lit_idx, nb);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(h->h_recount, h->d_recount, sizeof(int) * (NS + 1), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -2061,8 +2078,8 @@ static int solve_collect(ipc_engine* h, hipStream_t st, const CellPlan& pl, doub
             // (borderline cells beyond every cell kernel were solved by the cluster solver with the engine's term_eps; their
             // slot is not re-solved: counts of the long slots are skipped above because b < nb)
             hipLaunchKernelGGL(k_scatter_literal, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total,
-                               (const unsigned*)h->d_slot_off, NS, (const int*)h->d_recount, (const int*)h->d_lit_idx, (const double*)h->d_lit_chi,
-                               (const double*)h->d_lit_chitot, (const int4*)h->d_lit_meta, h->d_chi, h->d_chitot, h->d_meta);
+                               (const unsigned*)h->d_slot_off, NS, (const int*)h->d_recount, (const int*)h->cells.d_lit_idx, (const double*)h->cells.d_lit_chi,
+                               (const double*)h->cells.d_lit_chitot, (const int4*)h->cells.d_lit_meta, h->cells.d_chi, h->cells.d_chitot, h->cells.d_meta);
             HIPCHK(hipGetLastError());
             h->last_literal_cells += n_lit;
         }
@@ -2131,20 +2148,20 @@ static int solve_rows_impl(ipc_engine* h, int rank, int world, uint64_t* d_upper
     if (int rc = solve_planned(h, st, pl)) return rc;
     if (total)
         hipLaunchKernelGGL(k_scatter_bits, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total,
-                           h->d_cells, h->d_chi, h->prm.fast_reject_th, h->prm.slow_reject_th, rpr, (const int*)h->d_slot, words,
+                           h->cells.d_cells, h->cells.d_chi, h->prm.fast_reject_th, h->prm.slow_reject_th, rpr, (const int*)h->d_slot, words,
                            (unsigned long long*)d_upper);
     HIPCHK(hipGetLastError());
     if (total && !cached && phase == 0 && h->slow_first_iterations > 0) {
         // this step built the cell lists: its iteration counts order them for the steps to come (slow cells first)
         const unsigned nblk1 = (unsigned)((total + 1 + 255) / 256), nblk = (unsigned)((total + 255) / 256);
-        hipLaunchKernelGGL(k_slow_flags, dim3(nblk1), dim3(256), 0, st, (int)total, (const int4*)h->d_meta, h->slow_first_iterations, h->d_lit_idx);
-        hipLaunchKernelGGL(k_scan_int, dim3(1), dim3(1024), 0, st, h->d_lit_idx, (int)total + 1);
-        hipLaunchKernelGGL(k_slow_first_permute, dim3(nblk), dim3(256), 0, st, (int)total, (const unsigned*)h->d_slot_off, NS, (const int*)h->d_lit_idx,
-                           (const int2*)h->d_cells, (const double*)h->d_chi, (const double*)h->d_chitot, (const int4*)h->d_meta, h->d_lit_cells,
-                           h->d_lit_chi, h->d_lit_chitot, h->d_lit_meta);
+        hipLaunchKernelGGL(k_slow_flags, dim3(nblk1), dim3(256), 0, st, (int)total, (const int4*)h->cells.d_meta, h->slow_first_iterations, h->cells.d_lit_idx);
+        hipLaunchKernelGGL(k_scan_int, dim3(1), dim3(1024), 0, st, h->cells.d_lit_idx, (int)total + 1);
+        hipLaunchKernelGGL(k_slow_first_permute, dim3(nblk), dim3(256), 0, st, (int)total, (const unsigned*)h->d_slot_off, NS, (const int*)h->cells.d_lit_idx,
+                           (const int2*)h->cells.d_cells, (const double*)h->cells.d_chi, (const double*)h->cells.d_chitot, (const int4*)h->cells.d_meta, h->cells.d_lit_cells,
+                           h->cells.d_lit_chi, h->cells.d_lit_chitot, h->cells.d_lit_meta);
         HIPCHK(hipGetLastError());
-        std::swap(h->d_cells, h->d_lit_cells); std::swap(h->d_chi, h->d_lit_chi);
-        std::swap(h->d_chitot, h->d_lit_chitot); std::swap(h->d_meta, h->d_lit_meta);
+        std::swap(h->cells.d_cells, h->cells.d_lit_cells); std::swap(h->cells.d_chi, h->cells.d_lit_chi);
+        std::swap(h->cells.d_chitot, h->cells.d_lit_chitot); std::swap(h->cells.d_meta, h->cells.d_lit_meta);
     }
     return IPC_OK;
 }
@@ -2166,6 +2183,10 @@ extern "C" int ipc_assemble_matrix(ipc_engine_t* h, const uint64_t* d_gathered, 
     return IPC_OK;
 }
 
+// The set-max kernels keep the accepted mask of one list, a word per 64 candidates, in LDS.
+constexpr size_t kMaskLdsBytes = 60 * 1024;
+static bool mask_fits_lds(int n) { return sizeof(unsigned long long) * (size_t)((n + 63) / 64) <= kMaskLdsBytes; }
+
 extern "C" int ipc_set_max(ipc_engine_t* h, const uint64_t* d_bits, uint8_t* d_accepted, void* stream)
 {
     if (!h || !d_bits || !d_accepted) return fail(IPC_ERR_ARG, "ipc_set_max: NULL argument");
@@ -2174,7 +2195,7 @@ extern "C" int ipc_set_max(ipc_engine_t* h, const uint64_t* d_bits, uint8_t* d_a
     hipStream_t st = stream ? (hipStream_t)stream : h->own_stream;
     const int N = h->N, words = (N + 63) / 64;
     const size_t shmem = sizeof(unsigned long long) * words;
-    if (shmem > 60 * 1024) return fail(IPC_ERR_LIMIT, "ipc_set_max: N=%d exceeds the LDS-resident mask", N);
+    if (!mask_fits_lds(N)) return fail(IPC_ERR_LIMIT, "ipc_set_max: N=%d exceeds the LDS-resident mask", N);
     if (int rc = matrix_mode_enter(h, st)) return rc;
     hipLaunchKernelGGL(k_set_max, dim3(1), dim3(1024), shmem, st, N, words, words, (const int*)h->d_order,
                        (const unsigned long long*)d_bits, d_accepted, h->d_live, 0, (unsigned long long*)nullptr, (int*)nullptr);
@@ -2182,15 +2203,32 @@ extern "C" int ipc_set_max(ipc_engine_t* h, const uint64_t* d_bits, uint8_t* d_a
     return IPC_OK;
 }
 
-// scratch of ipc_run and its relatives: upper triangle, matrix, accepted bytes for N candidates (need = N * words)
-static int ensure_run_scratch(ipc_engine* h, int N, size_t need)
+// scratch of ipc_run and its relatives: upper triangle, matrix, accepted bytes for the N candidates of the moment
+static size_t run_words(const ipc_engine* h) { return (size_t)h->N * ((h->N + 63) / 64); }
+static int ensure_run_scratch(ipc_engine* h)
 {
-    if (need <= h->run_cap) return IPC_OK;
-    h->run_cap = 0;                                                // (until all three are there: a failure part way comes here again)
-    HIPCHK(h->d_upper.alloc(need));
-    HIPCHK(h->d_bits.alloc(need));
-    HIPCHK(h->d_acc.alloc((size_t)N + 64));
-    h->run_cap = need;
+    const size_t need = run_words(h);
+    HIPCHK(h->run.cap.grow(need, sized(h->run.d_upper, need), sized(h->run.d_bits, need), sized(h->run.d_acc, (size_t)h->N + 64)));
+    return IPC_OK;
+}
+
+// Every row as rank 0 of 1 into the run scratch, assembled into run.d_bits, on own_stream.  diag_cells, unless NULL: the set-only
+// order -- the diagonal cells (counted there), then the pair cells among the candidates that passed.
+static int run_matrix(ipc_engine* h, int* diag_cells = nullptr)
+{
+    if (diag_cells) {
+        if (int rc = solve_rows_impl(h, 0, 1, h->run.d_upper, h->own_stream, 1)) return rc;
+        *diag_cells = h->last_cells;
+    }
+    if (int rc = solve_rows_impl(h, 0, 1, h->run.d_upper, h->own_stream, diag_cells ? 2 : 0)) return rc;
+    return ipc_assemble_matrix(h, h->run.d_upper, 1, h->run.d_bits, h->own_stream);
+}
+
+// the matrix of the run scratch and the accepted bytes in d_accepted to the caller, where asked for (behind the host's wait)
+static int run_copy_out(ipc_engine* h, uint64_t* bits_out, uint8_t* accepted_out, const unsigned char* d_accepted)
+{
+    if (bits_out) HIPCHK(hipMemcpy(bits_out, h->run.d_bits, sizeof(uint64_t) * run_words(h), hipMemcpyDeviceToHost));
+    if (accepted_out) HIPCHK(hipMemcpy(accepted_out, d_accepted, (size_t)h->N, hipMemcpyDeviceToHost));
     return IPC_OK;
 }
 
@@ -2199,19 +2237,11 @@ extern "C" int ipc_run(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accepted_ou
     if (!h) return fail(IPC_ERR_ARG, "ipc_run: NULL handle");
     if (h->N <= 0) return fail(IPC_ERR_STATE, "ipc_run: no candidates set");
     HIPCHK(hipSetDevice(h->device));
-    const int N = h->N, words = (N + 63) / 64;
-    const size_t need = (size_t)N * words;
-    if (int rc = ensure_run_scratch(h, N, need)) return rc;
-    int rc = ipc_solve_rows(h, 0, 1, h->d_upper, h->own_stream);
-    if (rc) return rc;
-    rc = ipc_assemble_matrix(h, h->d_upper, 1, h->d_bits, h->own_stream);
-    if (rc) return rc;
-    rc = ipc_set_max(h, h->d_bits, h->d_acc, h->own_stream);
-    if (rc) return rc;
+    if (int rc = ensure_run_scratch(h)) return rc;
+    if (int rc = run_matrix(h)) return rc;
+    if (int rc = ipc_set_max(h, h->run.d_bits, h->run.d_acc, h->own_stream)) return rc;
     HIPCHK(hipStreamSynchronize(h->own_stream));
-    if (bits_out) HIPCHK(hipMemcpy(bits_out, h->d_bits, sizeof(uint64_t) * need, hipMemcpyDeviceToHost));
-    if (accepted_out) HIPCHK(hipMemcpy(accepted_out, h->d_acc, (size_t)N, hipMemcpyDeviceToHost));
-    return IPC_OK;
+    return run_copy_out(h, bits_out, accepted_out, h->run.d_acc);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2220,18 +2250,9 @@ extern "C" int ipc_run(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accepted_ou
 // workspace for N candidates: within what it holds a call allocates nothing
 static int ensure_multistart_scratch(ipc_engine* h, int N, size_t need)
 {
-    if (need > h->ms_mat_cap) {
-        h->ms_mat_cap = 0;
-        HIPCHK(h->d_ms_P.alloc(need));
-        h->ms_mat_cap = need;
-    }
-    if (N > h->ms_vec_cap) {
-        h->ms_vec_cap = 0;
-        HIPCHK(h->d_ms_vec.alloc(4 * (size_t)N));
-        HIPCHK(h->d_ms_acc.alloc((size_t)N));
-        h->ms_vec_cap = N;
-    }
-    if (!h->d_ms_info) HIPCHK(h->d_ms_info.alloc(kMsInfo));
+    HIPCHK(h->ms.mat.grow(need, sized(h->ms.d_P, need)));
+    HIPCHK(h->ms.vec.grow(N, sized(h->ms.d_vec, 4 * (size_t)N), sized(h->ms.d_acc, N)));
+    if (!h->ms.d_info) HIPCHK(h->ms.d_info.alloc(kMsInfo));
     return IPC_OK;
 }
 
@@ -2240,29 +2261,28 @@ static int set_max_multistart(ipc_engine* h, const uint64_t* d_bits, int stride,
 {
     const int N = h->N, words = (N + 63) / 64;
     const size_t row_bytes = sizeof(unsigned long long) * words;
-    if (row_bytes > 60 * 1024) return fail(IPC_ERR_LIMIT, "ipc_set_max_multistart: N=%d exceeds the LDS-resident mask", N);
+    if (!mask_fits_lds(N)) return fail(IPC_ERR_LIMIT, "ipc_set_max_multistart: N=%d exceeds the LDS-resident mask", N);
     if (int rc = matrix_mode_enter(h, st)) return rc;
     if (int rc = ensure_multistart_scratch(h, N, (size_t)N * words)) return rc;
-    const int cap = h->ms_vec_cap;
-    int* live = h->d_ms_vec; int* pos = live + cap; int* sz = pos + cap;
+    int* live = h->ms.live(); int* pos = h->ms.pos(); int* sz = h->ms.sz();
     const unsigned long long* C = (const unsigned long long*)d_bits;
-    hipLaunchKernelGGL(k_ms_live, dim3(1), dim3(1024), 0, st, N, stride, (const int*)h->d_order, C, live, pos, h->d_ms_info);
+    hipLaunchKernelGGL(k_ms_live, dim3(1), dim3(1024), 0, st, N, stride, (const int*)h->d_order, C, live, pos, h->ms.d_info);
     const dim3 grid((N + kMsWaves - 1) / kMsWaves), block(64 * kMsWaves);
-    hipLaunchKernelGGL(k_ms_compact, grid, block, 0, st, words, stride, C, (const int*)live, (const int*)h->d_ms_info, h->d_ms_P);
+    hipLaunchKernelGGL(k_ms_compact, grid, block, 0, st, words, stride, C, (const int*)live, (const int*)h->ms.d_info, h->ms.d_P);
     // cand in registers while a lane's share of the words is within the knob, else in LDS: as many waves per workgroup as
     // 60 KB of slices hold, four at the most (one at the N limit)
     const int per_lane = (words + 63) / 64;
     if (per_lane <= h->ms_reg_words && per_lane == 1)
-        hipLaunchKernelGGL(k_ms_greedy_reg<1>, grid, block, 0, st, words, (const unsigned long long*)h->d_ms_P, (const int*)h->d_ms_info, sz);
+        hipLaunchKernelGGL(k_ms_greedy_reg<1>, grid, block, 0, st, words, (const unsigned long long*)h->ms.d_P, (const int*)h->ms.d_info, sz);
     else if (per_lane <= h->ms_reg_words)
-        hipLaunchKernelGGL(k_ms_greedy_reg<2>, grid, block, 0, st, words, (const unsigned long long*)h->d_ms_P, (const int*)h->d_ms_info, sz);
+        hipLaunchKernelGGL(k_ms_greedy_reg<2>, grid, block, 0, st, words, (const unsigned long long*)h->ms.d_P, (const int*)h->ms.d_info, sz);
     else {
-        const int wpb = (int)std::min<size_t>(kMsWaves, (60 * 1024) / row_bytes);
+        const int wpb = (int)std::min<size_t>(kMsWaves, kMaskLdsBytes / row_bytes);
         hipLaunchKernelGGL(k_ms_greedy_lds, dim3((N + wpb - 1) / wpb), dim3(64 * wpb), row_bytes * wpb, st, words, wpb,
-                           (const unsigned long long*)h->d_ms_P, (const int*)h->d_ms_info, sz);
+                           (const unsigned long long*)h->ms.d_P, (const int*)h->ms.d_info, sz);
     }
-    hipLaunchKernelGGL(k_ms_pick, dim3(1), dim3(1024), row_bytes, st, N, words, (const unsigned long long*)h->d_ms_P, (const int*)live,
-                       (const int*)pos, (const int*)sz, h->d_ms_info, d_accepted, d_sizes);
+    hipLaunchKernelGGL(k_ms_pick, dim3(1), dim3(1024), row_bytes, st, N, words, (const unsigned long long*)h->ms.d_P, (const int*)live,
+                       (const int*)pos, (const int*)sz, h->ms.d_info, d_accepted, d_sizes);
     HIPCHK(hipGetLastError());
     return IPC_OK;
 }
@@ -2281,30 +2301,23 @@ extern "C" int ipc_run_multistart(ipc_engine_t* h, uint64_t* bits_out, uint8_t* 
     if (!h) return fail(IPC_ERR_ARG, "ipc_run_multistart: NULL handle");
     if (h->N <= 0) return fail(IPC_ERR_STATE, "ipc_run_multistart: no candidates set");
     HIPCHK(hipSetDevice(h->device));
-    const int N = h->N, words = (N + 63) / 64;
-    const size_t need = (size_t)N * words;
-    if (sizeof(unsigned long long) * (size_t)words > 60 * 1024) return fail(IPC_ERR_LIMIT, "ipc_run_multistart: N=%d exceeds the LDS-resident mask", N);
-    if (int rc = ensure_run_scratch(h, N, need)) return rc;
-    if (int rc = ensure_multistart_scratch(h, N, need)) return rc;
-    int rc = ipc_solve_rows(h, 0, 1, h->d_upper, h->own_stream);
-    if (rc) return rc;
-    rc = ipc_assemble_matrix(h, h->d_upper, 1, h->d_bits, h->own_stream);
-    if (rc) return rc;
-    rc = ipc_set_max(h, h->d_bits, h->d_acc, h->own_stream);
-    if (rc) return rc;
-    int* d_sizes = h->d_ms_vec + 3 * (size_t)h->ms_vec_cap;
-    rc = ipc_set_max_multistart(h, h->d_bits, h->d_ms_acc, d_sizes, h->own_stream);
-    if (rc) return rc;
+    const int N = h->N;
+    if (!mask_fits_lds(N)) return fail(IPC_ERR_LIMIT, "ipc_run_multistart: N=%d exceeds the LDS-resident mask", N);
+    if (int rc = ensure_run_scratch(h)) return rc;
+    if (int rc = ensure_multistart_scratch(h, N, run_words(h))) return rc;
+    if (int rc = run_matrix(h)) return rc;
+    if (int rc = ipc_set_max(h, h->run.d_bits, h->run.d_acc, h->own_stream)) return rc;
+    int* d_sizes = h->ms.sizes();
+    if (int rc = ipc_set_max_multistart(h, h->run.d_bits, h->ms.d_acc, d_sizes, h->own_stream)) return rc;
     HIPCHK(hipStreamSynchronize(h->own_stream));
-    if (bits_out) HIPCHK(hipMemcpy(bits_out, h->d_bits, sizeof(uint64_t) * need, hipMemcpyDeviceToHost));
-    if (accepted_out) HIPCHK(hipMemcpy(accepted_out, h->d_ms_acc, (size_t)N, hipMemcpyDeviceToHost));
-    if (greedy_out) HIPCHK(hipMemcpy(greedy_out, h->d_acc, (size_t)N, hipMemcpyDeviceToHost));
+    if (int rc = run_copy_out(h, bits_out, accepted_out, h->ms.d_acc)) return rc;
+    if (greedy_out) HIPCHK(hipMemcpy(greedy_out, h->run.d_acc, (size_t)N, hipMemcpyDeviceToHost));
     if (sizes_out) HIPCHK(hipMemcpy(sizes_out, d_sizes, sizeof(int32_t) * (size_t)N, hipMemcpyDeviceToHost));
     if (report) {
         int info[kMsInfo];
         std::vector<unsigned char> greedy((size_t)N);
-        HIPCHK(hipMemcpy(info, h->d_ms_info, sizeof(info), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(greedy.data(), h->d_acc, (size_t)N, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(info, h->ms.d_info, sizeof(info), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(greedy.data(), h->run.d_acc, (size_t)N, hipMemcpyDeviceToHost));
         int g = 0;
         for (unsigned char a : greedy) g += a ? 1 : 0;
         report->live = info[0]; report->greedy_size = g; report->best_size = info[1];
@@ -2320,6 +2333,47 @@ constexpr int kExLimitN = 8192;                        // a row of the compact m
 constexpr int kExPool = 2048, kExPoolFloor = 256;      // waves of k_ex_search: as many as subproblems up to kExPool, halved
 constexpr size_t kExPoolBytes = (size_t)2 << 30;       // ... down to kExPoolFloor while their stacks exceed this
 
+// a kernel that keeps one or two words of a row per lane (kExLimitN), by the width of the compact matrix
+#define IPC_EX_LAUNCH(kernel, words, grid, block, st, ...)                                 \
+    do {                                                                                   \
+        if ((words) <= 64) hipLaunchKernelGGL(kernel<1>, grid, block, 0, st, __VA_ARGS__); \
+        else hipLaunchKernelGGL(kernel<2>, grid, block, 0, st, __VA_ARGS__);               \
+    } while (0)
+
+// flags, sizes and steps by subproblem, for N candidates
+static int ensure_exact_vectors(ipc_engine* h, int N)
+{
+    HIPCHK(h->ex.vec.grow(N, sized(h->ex.d_vec, 3 * (size_t)N)));
+    return IPC_OK;
+}
+
+static long long exact_steps(int lo, int hi) { return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo); }
+
+// The workspace of a search from `roots` roots, `levels` deep, over n live candidates: the wave pool's stacks and a clique per
+// root.  What it lacks is refused beyond a quarter of the free memory (`who` and `what` as the caller words it) before it grows.
+struct ExactSearch { int levels, level_words; size_t slice_words; dim3 grid, block; };
+static int exact_workspace(ipc_engine* h, int roots, int n, int words, int levels, const char* who, const char* what, ExactSearch& S)
+{
+    auto& x = h->ex;
+    const int level_words = 64 * (words <= 64 ? 1 : 2) + (n + 3) / 4 + 1;
+    const size_t slice_words = (size_t)levels * level_words + (size_t)(levels + 1) / 2;
+    int pool = std::min(kExPool, (roots + kExWaves - 1) / kExWaves * kExWaves);
+    while (pool > kExPoolFloor && pool * slice_words * 8 > kExPoolBytes) pool /= 2;
+    const size_t need_ws = pool * slice_words, need_clq = (size_t)roots * levels;
+    if (need_ws > x.ws.size() || need_clq > x.clq.size()) {
+        size_t mem_free = 0, mem_total = 0;
+        HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
+        const size_t bytes = (need_ws > x.ws.size() ? need_ws * 8 : 0) + (need_clq > x.clq.size() ? need_clq * 2 : 0);
+        if (bytes > mem_free / 4)
+            return fail(IPC_ERR_LIMIT, "%s: a search of %d levels over %d %s needs %zu MB, a quarter of the free memory is %zu MB", who, levels,
+                        roots, what, bytes >> 20, mem_free >> 22);
+    }
+    HIPCHK(x.ws.grow(need_ws, sized(x.d_ws, need_ws)));
+    HIPCHK(x.clq.grow(need_clq, sized(x.d_clq, need_clq)));
+    S = ExactSearch{levels, level_words, slice_words, dim3(pool / kExWaves), dim3(64 * kExWaves)};
+    return IPC_OK;
+}
+
 // The multi-start set into d_accepted, UB0, then -- unless that already closes the bracket -- the search and the pick.  Blocks the
 // host twice: once to size the workspace from n, LB and UB0, once for the report.  ms_host, unless NULL, gets the multi-start set.
 static int set_max_exact(ipc_engine* h, const uint64_t* d_bits, int stride, uint8_t* d_accepted, ipc_exact_report_t* report,
@@ -2327,67 +2381,33 @@ static int set_max_exact(ipc_engine* h, const uint64_t* d_bits, int stride, uint
 {
     const int N = h->N, words = (N + 63) / 64;
     if (int rc = set_max_multistart(h, d_bits, stride, d_accepted, nullptr, st)) return rc;
-    if (N > h->ex_vec_cap) {
-        h->ex_vec_cap = 0;
-        HIPCHK(h->d_ex_vec.alloc(3 * (size_t)N));
-        h->ex_vec_cap = N;
-    }
-    if (!h->d_ex_info) HIPCHK(h->d_ex_info.alloc(kExInfo));
-    const unsigned long long* P = h->d_ms_P;
-    const int* ms_info = h->d_ms_info;
-    const bool one = words <= 64;
-    if (one) hipLaunchKernelGGL(k_ex_bound<1>, dim3(1), dim3(64), 0, st, words, P, ms_info, (int*)h->d_ex_info);
-    else hipLaunchKernelGGL(k_ex_bound<2>, dim3(1), dim3(64), 0, st, words, P, ms_info, (int*)h->d_ex_info);
+    if (int rc = ensure_exact_vectors(h, N)) return rc;
+    if (!h->ex.d_info) HIPCHK(h->ex.d_info.alloc(kExInfo));
+    const unsigned long long* P = h->ms.d_P;
+    const int* ms_info = h->ms.d_info;
+    IPC_EX_LAUNCH(k_ex_bound, words, dim3(1), dim3(64), st, words, P, ms_info, (int*)h->ex.d_info);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     int ms[kMsInfo], ex[kExInfo] = {0};
-    HIPCHK(hipMemcpy(ms, h->d_ms_info, sizeof(ms), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(ex, h->d_ex_info, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ms, h->ms.d_info, sizeof(ms), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ex, h->ex.d_info, sizeof(int), hipMemcpyDeviceToHost));
     if (ms_host) HIPCHK(hipMemcpy(ms_host, d_accepted, (size_t)N, hipMemcpyDeviceToHost));
     const int n = ms[0], lb = ms[1], ub0 = ex[0];
     ipc_exact_report_t rep{};
     rep.live = n; rep.multistart_size = lb; rep.size = lb; rep.upper_bound = ub0; rep.proven = lb >= ub0 ? 1 : 0;
     if (lb < ub0) {
-        const int levels = std::min(ub0, n);
-        const int level_words = 64 * (one ? 1 : 2) + (n + 3) / 4 + 1;
-        const size_t slice_words = (size_t)levels * level_words + (size_t)(levels + 1) / 2;
-        int pool = std::min(kExPool, (n + kExWaves - 1) / kExWaves * kExWaves);
-        while (pool > kExPoolFloor && pool * slice_words * 8 > kExPoolBytes) pool /= 2;
-        const size_t need_ws = pool * slice_words, need_clq = (size_t)n * levels;
-        if (need_ws > h->ex_ws_cap || need_clq > h->ex_clq_cap) {
-            size_t mem_free = 0, mem_total = 0;
-            HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
-            const size_t bytes = (need_ws > h->ex_ws_cap ? need_ws * 8 : 0) + (need_clq > h->ex_clq_cap ? need_clq * 2 : 0);
-            if (bytes > mem_free / 4)
-                return fail(IPC_ERR_LIMIT, "ipc_set_max_exact: a search of %d levels over %d live candidates needs %zu MB, a quarter of the free memory is %zu MB",
-                            levels, n, bytes >> 20, mem_free >> 22);
-        }
-        if (need_ws > h->ex_ws_cap) {
-            h->ex_ws_cap = 0;
-            HIPCHK(h->d_ex_ws.alloc(need_ws));
-            h->ex_ws_cap = need_ws;
-        }
-        if (need_clq > h->ex_clq_cap) {
-            h->ex_clq_cap = 0;
-            HIPCHK(h->d_ex_clq.alloc(need_clq));
-            h->ex_clq_cap = need_clq;
-        }
-        const int cap = h->ex_vec_cap;
-        int* flag = h->d_ex_vec; int* size = flag + cap; unsigned* steps = (unsigned*)(size + cap);
-        const dim3 grid(pool / kExWaves), block(64 * kExWaves);
-        if (one)
-            hipLaunchKernelGGL(k_ex_search<1>, grid, block, 0, st, words, levels, level_words, slice_words, h->ex_step_cap, P, ms_info,
-                               (int*)h->d_ex_info, (unsigned long long*)h->d_ex_ws, flag, size, steps, (unsigned short*)h->d_ex_clq);
-        else
-            hipLaunchKernelGGL(k_ex_search<2>, grid, block, 0, st, words, levels, level_words, slice_words, h->ex_step_cap, P, ms_info,
-                               (int*)h->d_ex_info, (unsigned long long*)h->d_ex_ws, flag, size, steps, (unsigned short*)h->d_ex_clq);
-        hipLaunchKernelGGL(k_ex_pick, dim3(1), dim3(1024), 0, st, N, levels, (const int*)h->d_ms_vec, ms_info, (const int*)flag,
-                           (const int*)size, (const unsigned*)steps, (const unsigned short*)h->d_ex_clq, (int*)h->d_ex_info, d_accepted);
+        ExactSearch S;
+        if (int rc = exact_workspace(h, n, n, words, std::min(ub0, n), "ipc_set_max_exact", "live candidates", S)) return rc;
+        int* flag = h->ex.flag(); int* size = h->ex.sizes(); unsigned* steps = h->ex.steps();
+        IPC_EX_LAUNCH(k_ex_search, words, S.grid, S.block, st, words, S.levels, S.level_words, S.slice_words, h->ex_step_cap, P, ms_info,
+                      (int*)h->ex.d_info, (unsigned long long*)h->ex.d_ws, flag, size, steps, (unsigned short*)h->ex.d_clq);
+        hipLaunchKernelGGL(k_ex_pick, dim3(1), dim3(1024), 0, st, N, S.levels, (const int*)h->ms.live(), ms_info, (const int*)flag,
+                           (const int*)size, (const unsigned*)steps, (const unsigned short*)h->ex.d_clq, (int*)h->ex.d_info, d_accepted);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipMemcpy(ex, h->d_ex_info, sizeof(ex), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(ex, h->ex.d_info, sizeof(ex), hipMemcpyDeviceToHost));
         rep.subproblems = ex[4]; rep.capped = ex[5];
-        rep.steps = (long long)(((unsigned long long)(unsigned)ex[7] << 32) | (unsigned)ex[6]);
+        rep.steps = exact_steps(ex[6], ex[7]);
         if (rep.capped == 0) { rep.proven = 1; rep.size = rep.upper_bound = ex[2]; }
     }
     if (report) *report = rep;
@@ -2409,19 +2429,11 @@ extern "C" int ipc_run_exact(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accep
     if (h->N <= 0) return fail(IPC_ERR_STATE, "ipc_run_exact: no candidates set");
     if (h->N > kExLimitN) return fail(IPC_ERR_LIMIT, "ipc_run_exact: N=%d exceeds %d candidates", h->N, kExLimitN);
     HIPCHK(hipSetDevice(h->device));
-    const int N = h->N, words = (N + 63) / 64;
-    const size_t need = (size_t)N * words;
-    if (int rc = ensure_run_scratch(h, N, need)) return rc;
-    if (int rc = ensure_multistart_scratch(h, N, need)) return rc;
-    int rc = ipc_solve_rows(h, 0, 1, h->d_upper, h->own_stream);
-    if (rc) return rc;
-    rc = ipc_assemble_matrix(h, h->d_upper, 1, h->d_bits, h->own_stream);
-    if (rc) return rc;
-    rc = set_max_exact(h, h->d_bits, words, h->d_ms_acc, report, h->own_stream, multistart_out);
-    if (rc) return rc;
-    if (bits_out) HIPCHK(hipMemcpy(bits_out, h->d_bits, sizeof(uint64_t) * need, hipMemcpyDeviceToHost));
-    if (accepted_out) HIPCHK(hipMemcpy(accepted_out, h->d_ms_acc, (size_t)N, hipMemcpyDeviceToHost));
-    return IPC_OK;
+    if (int rc = ensure_run_scratch(h)) return rc;
+    if (int rc = ensure_multistart_scratch(h, h->N, run_words(h))) return rc;
+    if (int rc = run_matrix(h)) return rc;
+    if (int rc = set_max_exact(h, h->run.d_bits, (h->N + 63) / 64, h->ms.d_acc, report, h->own_stream, multistart_out)) return rc;
+    return run_copy_out(h, bits_out, accepted_out, h->ms.d_acc);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2435,34 +2447,21 @@ static int set_max_exact_resume(ipc_engine* h, const uint64_t* d_bits, int strid
 {
     const int N = h->N, words = (N + 63) / 64;
     if (int rc = ensure_multistart_scratch(h, N, (size_t)N * words)) return rc;
-    if (int rc = set_max_multistart(h, d_bits, stride, h->d_ms_acc, nullptr, st)) return rc;
-    if (N > h->ex_vec_cap) {
-        h->ex_vec_cap = 0;
-        HIPCHK(h->d_ex_vec.alloc(3 * (size_t)N));
-        h->ex_vec_cap = N;
-    }
-    if (N > h->exr_roots_cap) {
-        h->exr_roots_cap = 0;
-        HIPCHK(h->d_exr_roots.alloc((size_t)N));
-        h->exr_roots_cap = N;
-    }
-    if (!h->d_exr_info) HIPCHK(h->d_exr_info.alloc(kExrInfo));
-    if (!h->d_exr_new) HIPCHK(h->d_exr_new.alloc((kExLimitN + 63) / 64));
-    const unsigned long long* P = h->d_ms_P;
-    const int* ms_info = h->d_ms_info;
-    const int* live = h->d_ms_vec; const int* pos = live + h->ms_vec_cap;
-    int* info = h->d_exr_info;
-    const bool one = words <= 64;
-    if (one)
-        hipLaunchKernelGGL(k_exr_prepare<1>, dim3(1), dim3(1024), 0, st, N, first, words, P, live, pos, ms_info, (const unsigned char*)d_accepted,
-                           (unsigned long long*)h->d_exr_new, (int*)h->d_exr_roots, info);
-    else
-        hipLaunchKernelGGL(k_exr_prepare<2>, dim3(1), dim3(1024), 0, st, N, first, words, P, live, pos, ms_info, (const unsigned char*)d_accepted,
-                           (unsigned long long*)h->d_exr_new, (int*)h->d_exr_roots, info);
+    if (int rc = set_max_multistart(h, d_bits, stride, h->ms.d_acc, nullptr, st)) return rc;
+    if (int rc = ensure_exact_vectors(h, N)) return rc;
+    HIPCHK(h->ex.roots.grow(N, sized(h->ex.d_roots, N)));
+    if (!h->ex.d_rinfo) HIPCHK(h->ex.d_rinfo.alloc(kExrInfo));
+    if (!h->ex.d_new) HIPCHK(h->ex.d_new.alloc((kExLimitN + 63) / 64));
+    const unsigned long long* P = h->ms.d_P;
+    const int* ms_info = h->ms.d_info;
+    const int* live = h->ms.live(); const int* pos = h->ms.pos();
+    int* info = h->ex.d_rinfo;
+    IPC_EX_LAUNCH(k_exr_prepare, words, dim3(1), dim3(1024), st, N, first, words, P, live, pos, ms_info, (const unsigned char*)d_accepted,
+                  (unsigned long long*)h->ex.d_new, (int*)h->ex.d_roots, info);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     int ms[kMsInfo], ex[kExrInfo] = {0};
-    HIPCHK(hipMemcpy(ms, h->d_ms_info, sizeof(ms), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ms, h->ms.d_info, sizeof(ms), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(ex, info, sizeof(int) * 4, hipMemcpyDeviceToHost));
     if (!ex[0])
         return fail(IPC_ERR_ARG, "ipc_set_max_exact_resume: d_accepted is not a set of pairwise consistent live candidates in front of first=%d", first);
@@ -2472,53 +2471,20 @@ static int set_max_exact_resume(ipc_engine* h, const uint64_t* d_bits, int strid
     ipc_exact_resume_report_t rep{};
     rep.first = first; rep.live = n; rep.newcomers = m; rep.size_before = w0; rep.multistart_size = lb;
     if (search) {
-        const int levels = ub;
-        const int level_words = 64 * (one ? 1 : 2) + (n + 3) / 4 + 1;
-        const size_t slice_words = (size_t)levels * level_words + (size_t)(levels + 1) / 2;
-        int pool = std::min(kExPool, (m + kExWaves - 1) / kExWaves * kExWaves);
-        while (pool > kExPoolFloor && pool * slice_words * 8 > kExPoolBytes) pool /= 2;
-        const size_t need_ws = pool * slice_words, need_clq = (size_t)m * levels;
-        if (need_ws > h->ex_ws_cap || need_clq > h->ex_clq_cap) {
-            size_t mem_free = 0, mem_total = 0;
-            HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
-            const size_t bytes = (need_ws > h->ex_ws_cap ? need_ws * 8 : 0) + (need_clq > h->ex_clq_cap ? need_clq * 2 : 0);
-            if (bytes > mem_free / 4)
-                return fail(IPC_ERR_LIMIT, "ipc_set_max_exact_resume: a search of %d levels over %d newcomers needs %zu MB, a quarter of the free memory is %zu MB",
-                            levels, m, bytes >> 20, mem_free >> 22);
-        }
-        if (need_ws > h->ex_ws_cap) {
-            h->ex_ws_cap = 0;
-            HIPCHK(h->d_ex_ws.alloc(need_ws));
-            h->ex_ws_cap = need_ws;
-        }
-        if (need_clq > h->ex_clq_cap) {
-            h->ex_clq_cap = 0;
-            HIPCHK(h->d_ex_clq.alloc(need_clq));
-            h->ex_clq_cap = need_clq;
-        }
-        const int cap = h->ex_vec_cap;
-        int* flag = h->d_ex_vec; int* size = flag + cap; unsigned* steps = (unsigned*)(size + cap);
-        const dim3 grid(pool / kExWaves), block(64 * kExWaves);
-        if (one)
-            hipLaunchKernelGGL(k_exr_search<1>, grid, block, 0, st, words, levels, level_words, slice_words, h->ex_step_cap, P, ms_info, info,
-                               (const unsigned long long*)h->d_exr_new, (const int*)h->d_exr_roots, (unsigned long long*)h->d_ex_ws, flag, size,
-                               steps, (unsigned short*)h->d_ex_clq);
-        else
-            hipLaunchKernelGGL(k_exr_search<2>, grid, block, 0, st, words, levels, level_words, slice_words, h->ex_step_cap, P, ms_info, info,
-                               (const unsigned long long*)h->d_exr_new, (const int*)h->d_exr_roots, (unsigned long long*)h->d_ex_ws, flag, size,
-                               steps, (unsigned short*)h->d_ex_clq);
+        ExactSearch S;
+        if (int rc = exact_workspace(h, m, n, words, ub, "ipc_set_max_exact_resume", "newcomers", S)) return rc;
+        IPC_EX_LAUNCH(k_exr_search, words, S.grid, S.block, st, words, S.levels, S.level_words, S.slice_words, h->ex_step_cap, P, ms_info, info,
+                      (const unsigned long long*)h->ex.d_new, (const int*)h->ex.d_roots, (unsigned long long*)h->ex.d_ws, h->ex.flag(), h->ex.sizes(),
+                      h->ex.steps(), (unsigned short*)h->ex.d_clq);
     }
-    {
-        const int cap = h->ex_vec_cap;
-        const int* flag = h->d_ex_vec; const int* size = flag + cap; const unsigned* steps = (const unsigned*)(size + cap);
-        hipLaunchKernelGGL(k_exr_pick, dim3(1), dim3(1024), 0, st, N, search ? ub : 1, search ? 1 : 0, live, ms_info, flag, size, steps,
-                           (const unsigned short*)h->d_ex_clq, (const unsigned char*)h->d_ms_acc, info, d_accepted);
-    }
+    hipLaunchKernelGGL(k_exr_pick, dim3(1), dim3(1024), 0, st, N, search ? ub : 1, search ? 1 : 0, live, ms_info, (const int*)h->ex.flag(),
+                       (const int*)h->ex.sizes(), (const unsigned*)h->ex.steps(), (const unsigned short*)h->ex.d_clq,
+                       (const unsigned char*)h->ms.d_acc, info, d_accepted);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipMemcpy(ex, info, sizeof(ex), hipMemcpyDeviceToHost));
     rep.subproblems = ex[7]; rep.capped = ex[8];
-    rep.steps = (long long)(((unsigned long long)(unsigned)ex[10] << 32) | (unsigned)ex[9]);
+    rep.steps = exact_steps(ex[9], ex[10]);
     rep.changed = ex[11];
     rep.size = ex[5];
     if (rep.capped == 0) { rep.proven = 1; rep.upper_bound = rep.size; }
@@ -2594,7 +2560,7 @@ extern "C" int ipc_reserve_candidates(ipc_engine_t* h, int capacity)
     if (cap > h->reserved_cands) h->reserved_cands = cap;
     if (cap > h->cstride) { if (int rc = grow_candidates(h, cap)) return rc; }
     // (beyond the N limit of ipc_run_online only the candidate arrays are reserved: the faithful mode has no such limit)
-    if (cap > h->on_ccap && sizeof(unsigned long long) * (size_t)(cap / 64) <= 60 * 1024) { if (int rc = grow_online(h, cap)) return rc; }
+    if (cap > h->on_ccap && mask_fits_lds(cap)) { if (int rc = grow_online(h, cap)) return rc; }
     return IPC_OK;
 }
 
@@ -2619,7 +2585,7 @@ extern "C" int ipc_run_online(ipc_engine_t* h, uint64_t* bits_out, uint8_t* acce
     if (h->N <= 0) return fail(IPC_ERR_STATE, "ipc_run_online: no candidates set");
     HIPCHK(hipSetDevice(h->device));
     const int N = h->N, M = h->on_cov, words = (N + 63) / 64;
-    if (sizeof(unsigned long long) * (size_t)words > 60 * 1024) return fail(IPC_ERR_LIMIT, "ipc_run_online: N=%d exceeds the LDS-resident mask", N);
+    if (!mask_fits_lds(N)) return fail(IPC_ERR_LIMIT, "ipc_run_online: N=%d exceeds the LDS-resident mask", N);
     hipStream_t st = h->own_stream;
     if (int rc = matrix_mode_enter(h, st)) return rc;
     ipc_online_report_t rep{};
@@ -2650,8 +2616,8 @@ extern "C" int ipc_run_online(ipc_engine_t* h, uint64_t* bits_out, uint8_t* acce
         const size_t total = pl.total;
         if (int rc = solve_planned(h, st, pl)) return rc;
         if (total)
-            hipLaunchKernelGGL(k_scatter_bits_delta, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total, (const int2*)h->d_cells,
-                               (const double*)h->d_chi, h->prm.fast_reject_th, h->prm.slow_reject_th, stride, h->d_on_upper);
+            hipLaunchKernelGGL(k_scatter_bits_delta, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total, (const int2*)h->cells.d_cells,
+                               (const double*)h->cells.d_chi, h->prm.fast_reject_th, h->prm.slow_reject_th, stride, h->d_on_upper);
         const int tiles = ((N - 1) >> 6) + 1;
         hipLaunchKernelGGL(k_assemble_delta, dim3(words, std::min((tiles + 3) / 4, 1024)), dim3(256), 0, st, N, M, stride, (const int*)h->d_lo,
                            (const int*)h->d_hi, (const unsigned long long*)h->d_on_upper, h->d_on_bits);
@@ -2738,29 +2704,23 @@ static int sweep_first_pass(ipc_engine* h, hipStream_t st)
     if (int rc = plan_rows(h, st, 0, 1, 0, nullptr, false, pl, cached)) return rc;
     const size_t total = pl.total;
     h->sw_valid = false;
-    if (total > h->sw_cap) {
+    if (auto& w = h->sw; total > w.cap.size()) {
         const size_t cap = total + total / 8 + 1024;
-        h->sw_cap = 0;                                   // (until all six are there: a failure part way comes here again)
-        HIPCHK(h->d_sw_cells.alloc(cap));
-        HIPCHK(h->d_sw_chi.alloc(cap));
-        HIPCHK(h->d_sw_chitot.alloc(cap));
-        HIPCHK(h->d_sw_meta.alloc(cap));
-        HIPCHK(h->d_sw_lit.alloc(cap));
-        HIPCHK(h->d_sw_flags.alloc(cap));
-        h->sw_cap = cap;
+        HIPCHK(w.cap.grow(cap, sized(w.d_cells, cap), sized(w.d_chi, cap), sized(w.d_chitot, cap), sized(w.d_meta, cap), sized(w.d_lit, cap),
+                          sized(w.d_flags, cap)));
     }
     if (!h->d_sw_slot_off) HIPCHK(h->d_sw_slot_off.alloc(NS + 1));
     if (int rc = solve_first_pass(h, st, pl)) return rc;
     if (total)
-        hipLaunchKernelGGL(k_sweep_init_flags, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total, (const int4*)h->d_meta,
-                           h->lm_retry, h->d_sw_flags);
+        hipLaunchKernelGGL(k_sweep_init_flags, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total, (const int4*)h->cells.d_meta,
+                           h->lm_retry, h->sw.d_flags);
     HIPCHK(hipGetLastError());
     if (int rc = solve_collect(h, st, pl, 0.0)) return rc;     // (band 0: the failed cells alone)
-    HIPCHK(hipMemcpyAsync(h->d_sw_cells, h->d_cells, sizeof(int2) * total, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(h->d_sw_chi, h->d_chi, sizeof(double) * total, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(h->d_sw_chitot, h->d_chitot, sizeof(double) * total, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(h->d_sw_meta, h->d_meta, sizeof(int4) * total, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemsetAsync(h->d_sw_lit, 0, sizeof(double) * total, st));
+    HIPCHK(hipMemcpyAsync(h->sw.d_cells, h->cells.d_cells, sizeof(int2) * total, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(h->sw.d_chi, h->cells.d_chi, sizeof(double) * total, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(h->sw.d_chitot, h->cells.d_chitot, sizeof(double) * total, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(h->sw.d_meta, h->cells.d_meta, sizeof(int4) * total, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemsetAsync(h->sw.d_lit, 0, sizeof(double) * total, st));
     h->sw_counts.assign(pl.counts, pl.counts + NS);
     h->sw_offsets.assign(pl.offsets, pl.offsets + NS);
     unsigned slot_off[NS + 1];
@@ -2783,14 +2743,11 @@ static int sweep_literal(ipc_engine* h, hipStream_t st, int n_th, double band, i
     const size_t total = h->sw_total;
     n_new = 0;
     if (!total || !(band > 0.0)) return IPC_OK;
-    if (!h->d_failed || (int)total > h->failed_cap) {
-        h->failed_cap = std::max(16384, (int)(total + total / 8));
-        HIPCHK(h->d_failed.alloc((size_t)h->failed_cap + 1));
-    }
+    if (int rc = ensure_failed_list(h, total)) return rc;
     HIPCHK(hipMemsetAsync(h->d_recount, 0, sizeof(int) * (NS + 1), st));
-    hipLaunchKernelGGL(k_sweep_collect, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total, (const int*)h->d_sw_flags,
-                       (const double*)h->d_sw_chi, (const int2*)h->d_sw_cells, n_th, (const double*)h->d_sw_th, (const double*)h->d_sw_th + n_th,
-                       band, h->failed_cap, h->d_failed, h->d_recount, (const unsigned*)h->d_sw_slot_off, NS, h->d_lit_cells, h->d_lit_idx,
+    hipLaunchKernelGGL(k_sweep_collect, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total, (const int*)h->sw.d_flags,
+                       (const double*)h->sw.d_chi, (const int2*)h->sw.d_cells, n_th, (const double*)h->sw.d_th, (const double*)h->sw.d_th + n_th,
+                       band, (int)h->failed.cap.size(), h->failed.d_list, h->d_recount, (const unsigned*)h->d_sw_slot_off, NS, h->cells.d_lit_cells, h->cells.d_lit_idx,
                        h->plan.caps.n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h->h_recount, h->d_recount, sizeof(int) * (NS + 1), hipMemcpyDeviceToHost, st));
@@ -2800,26 +2757,26 @@ static int sweep_literal(ipc_engine* h, hipStream_t st, int n_th, double band, i
     if (n_lit) {
         if (int rc = launch_literal_lists(h, st, h->sw_offsets.data())) return rc;
         hipLaunchKernelGGL(k_sweep_keep_literal, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total,
-                           (const unsigned*)h->d_sw_slot_off, NS, (const int*)h->d_recount, (const int*)h->d_lit_idx, (const double*)h->d_lit_chi,
-                           h->d_sw_lit, h->d_sw_flags);
+                           (const unsigned*)h->d_sw_slot_off, NS, (const int*)h->d_recount, (const int*)h->cells.d_lit_idx, (const double*)h->cells.d_lit_chi,
+                           h->sw.d_lit, h->sw.d_flags);
         HIPCHK(hipGetLastError());
         n_new += n_lit; h->sw_held += n_lit;
     }
-    const int n_host = std::min(h->h_recount[NS], h->failed_cap);
+    const int n_host = std::min(h->h_recount[NS], (int)h->failed.cap.size());
     if (n_host) {
         if (int rc = ensure_incremental(h, "ipc_run_sweep")) return rc;
         HIPCHK(hipStreamSynchronize(st));
         std::vector<int> idx(n_host);
-        HIPCHK(hipMemcpy(idx.data(), h->d_failed, sizeof(int) * n_host, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(idx.data(), h->failed.d_list, sizeof(int) * n_host, hipMemcpyDeviceToHost));
         std::sort(idx.begin(), idx.end());
         for (int q = 0; q < n_host; ++q) {
             int2 cell;
-            HIPCHK(hipMemcpy(&cell, h->d_sw_cells + idx[q], sizeof(int2), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(&cell, h->sw.d_cells + idx[q], sizeof(int2), hipMemcpyDeviceToHost));
             ClusterOut o;
             if (int rc = host_cell_solve(h, cell, false, true, o)) return rc;      // g2o's literal trial loop, as resolve_failed_cells runs it
             const int held = kSweepHeld;
-            HIPCHK(hipMemcpy(h->d_sw_lit + idx[q], &o.max_chi2, sizeof(double), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(h->d_sw_flags + idx[q], &held, sizeof(int), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(h->sw.d_lit + idx[q], &o.max_chi2, sizeof(double), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(h->sw.d_flags + idx[q], &held, sizeof(int), hipMemcpyHostToDevice));
             ++h->sw_held; ++n_new;                       // (per cell: a failure part way leaves the count at what the flags say)
         }
         HIPCHK(hipStreamSynchronize(nullptr));                 // (NULL-stream copies are not ordered against the engine's non-blocking streams: copy_d2d_now)
@@ -2846,19 +2803,20 @@ extern "C" int ipc_run_sweep(ipc_engine_t* h, int n_th, const double* fast_th, c
     if (h->N <= 0) return fail(IPC_ERR_STATE, "ipc_run_sweep: no candidates set");
     HIPCHK(hipSetDevice(h->device));
     const int N = h->N, words = (N + 63) / 64;
-    if (sizeof(unsigned long long) * (size_t)words > 60 * 1024) return fail(IPC_ERR_LIMIT, "ipc_run_sweep: N=%d exceeds the LDS-resident mask", N);
+    if (!mask_fits_lds(N)) return fail(IPC_ERR_LIMIT, "ipc_run_sweep: N=%d exceeds the LDS-resident mask", N);
     hipStream_t st = h->own_stream;
     if (int rc = matrix_mode_enter(h, st)) return rc;
     // Chunks: a threshold costs an upper triangle, a matrix, the accepted bytes and the live list.  The scratch grows only when a
     // call needs more than it holds, up to a quarter of the free memory; nothing is allocated if not even one threshold fits.
     const size_t mat = (size_t)N * words;
     const int want = h->sweep_chunk > 0 ? std::min(n_th, h->sweep_chunk) : n_th;
-    int tc = (int)std::min<size_t>({(size_t)want, h->sw_mat_cap / mat, h->sw_vec_cap / (size_t)N});   // what the scratch holds
+    auto& w = h->sw;
+    int tc = (int)std::min<size_t>({(size_t)want, w.mat.size() / mat, w.vec.size() / (size_t)N});   // what the scratch holds
     if (tc < want) {
         size_t mem_free = 0, mem_total = 0;
         HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
         const size_t per = 2 * mat * sizeof(unsigned long long) + 5 * (size_t)N;
-        const size_t held = 2 * h->sw_mat_cap * sizeof(unsigned long long) + 5 * h->sw_vec_cap;     // (freed by the growth)
+        const size_t held = 2 * w.mat.size() * sizeof(unsigned long long) + 5 * w.vec.size();     // (freed by the growth)
         const size_t fit = ((mem_free + held) / 4) / per;
         if (std::max<size_t>(fit, tc) < 1)
             return fail(IPC_ERR_LIMIT, "ipc_run_sweep: one threshold of N=%d needs %zu MB of scratch, a quarter of the free memory is %zu MB",
@@ -2867,23 +2825,14 @@ extern "C" int ipc_run_sweep(ipc_engine_t* h, int n_th, const double* fast_th, c
         // (a scratch that holds some pairs is replaced only for the call's whole need or for twice what it holds: a budget that
         // wavers by a pair from call to call must not free and allocate the four arrays every time)
         if (grown > tc && (tc == 0 || grown == want || grown >= 2 * tc)) {
-            h->sw_mat_cap = h->sw_vec_cap = 0;           // (until all four are there: a failure part way comes here again)
-            h->d_sw_upper.reset(); h->d_sw_bits.reset(); h->d_sw_acc.reset(); h->d_sw_live.reset();
-            HIPCHK(h->d_sw_upper.alloc(mat * grown));
-            HIPCHK(h->d_sw_bits.alloc(mat * grown));
-            HIPCHK(h->d_sw_acc.alloc((size_t)N * grown));
-            HIPCHK(h->d_sw_live.alloc((size_t)N * grown));
-            h->sw_mat_cap = mat * grown; h->sw_vec_cap = (size_t)N * grown;
+            const size_t m = mat * grown, v = (size_t)N * grown;
+            HIPCHK(w.mat.regrow(m, sized(w.d_upper, m), sized(w.d_bits, m), sized(w.d_acc, v), sized(w.d_live, v), sized(w.vec, v)));
             tc = grown;
         }
     }
-    if (n_th > h->sw_th_cap) {
-        h->sw_th_cap = 0;
-        HIPCHK(h->d_sw_th.alloc(2 * (size_t)n_th));
-        h->sw_th_cap = n_th;
-    }
-    HIPCHK(hipMemcpyAsync(h->d_sw_th, fast_th, sizeof(double) * n_th, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(h->d_sw_th + n_th, slow_th, sizeof(double) * n_th, hipMemcpyHostToDevice, st));
+    HIPCHK(w.th.grow(n_th, sized(w.d_th, 2 * (size_t)n_th)));
+    HIPCHK(hipMemcpyAsync(h->sw.d_th, fast_th, sizeof(double) * n_th, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(h->sw.d_th + n_th, slow_th, sizeof(double) * n_th, hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));                    // (pageable sources: the copies have left the caller's arrays when this returns)
     ipc_sweep_report_t rep{};
     rep.thresholds = n_th;
@@ -2904,19 +2853,19 @@ extern "C" int ipc_run_sweep(ipc_engine_t* h, int n_th, const double* fast_th, c
     const int tiles = ((N - 1) >> 6) + 1;
     for (int t0 = 0; t0 < n_th; t0 += tc) {
         const int n = std::min(tc, n_th - t0);
-        HIPCHK(hipMemsetAsync(h->d_sw_upper, 0, sizeof(unsigned long long) * mat * n, st));
+        HIPCHK(hipMemsetAsync(h->sw.d_upper, 0, sizeof(unsigned long long) * mat * n, st));
         if (total)
-            hipLaunchKernelGGL(k_sweep_scatter, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total, (const int2*)h->d_sw_cells,
-                               (const double*)h->d_sw_chi, (const double*)h->d_sw_lit, (const int*)h->d_sw_flags, n, (const double*)h->d_sw_th + t0,
-                               (const double*)h->d_sw_th + n_th + t0, band, words, mat, h->d_sw_upper);
+            hipLaunchKernelGGL(k_sweep_scatter, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total, (const int2*)h->sw.d_cells,
+                               (const double*)h->sw.d_chi, (const double*)h->sw.d_lit, (const int*)h->sw.d_flags, n, (const double*)h->sw.d_th + t0,
+                               (const double*)h->sw.d_th + n_th + t0, band, words, mat, h->sw.d_upper);
         hipLaunchKernelGGL(k_sweep_assemble, dim3(words, std::min((tiles + 3) / 4, 1024), n), dim3(256), 0, st, N, words, mat, (const int*)h->d_lo,
-                           (const int*)h->d_hi, (const unsigned long long*)h->d_sw_upper, h->d_sw_bits);
+                           (const int*)h->d_hi, (const unsigned long long*)h->sw.d_upper, h->sw.d_bits);
         hipLaunchKernelGGL(k_sweep_set_max, dim3(n), dim3(1024), sizeof(unsigned long long) * words, st, N, words, mat, (const int*)h->d_order,
-                           (const unsigned long long*)h->d_sw_bits, h->d_sw_acc, h->d_sw_live);
+                           (const unsigned long long*)h->sw.d_bits, h->sw.d_acc, h->sw.d_live);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));
-        if (bits_out) HIPCHK(hipMemcpy(bits_out + (size_t)t0 * mat, h->d_sw_bits, sizeof(uint64_t) * mat * n, hipMemcpyDeviceToHost));
-        if (accepted_out) HIPCHK(hipMemcpy(accepted_out + (size_t)t0 * N, h->d_sw_acc, (size_t)N * n, hipMemcpyDeviceToHost));
+        if (bits_out) HIPCHK(hipMemcpy(bits_out + (size_t)t0 * mat, h->sw.d_bits, sizeof(uint64_t) * mat * n, hipMemcpyDeviceToHost));
+        if (accepted_out) HIPCHK(hipMemcpy(accepted_out + (size_t)t0 * N, h->sw.d_acc, (size_t)N * n, hipMemcpyDeviceToHost));
         ++rep.chunks;
     }
     if (report) *report = rep;
@@ -2950,7 +2899,7 @@ extern "C" int ipc_run_batch(ipc_engine_t* h, int n_runs, const int* run_offsets
         return 2 * n * words * sizeof(unsigned long long) + n * (1 + 5 * sizeof(int)) + (size_t)N * sizeof(int) + sizeof(BatchRun);
     };
     for (int r = 0; r < R; ++r)
-        if (sizeof(unsigned long long) * (size_t)((run_n(r) + 63) / 64) > 60 * 1024)
+        if (!mask_fits_lds(run_n(r)))
             return fail(IPC_ERR_LIMIT, "ipc_run_batch: run %d with %d candidates exceeds the LDS-resident mask", r, run_n(r));
     HIPCHK(hipSetDevice(h->device));
     // Chunks of consecutive runs: as many as fit a quarter of the free memory (the scratch the engine holds counts as free: a
@@ -2959,7 +2908,7 @@ extern "C" int ipc_run_batch(ipc_engine_t* h, int n_runs, const int* run_offsets
     {
         size_t mem_free = 0, mem_total = 0;
         HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
-        const size_t held = 2 * h->bt_mat_cap * sizeof(unsigned long long) + h->bt_vec_cap * (1 + 5 * sizeof(int)) + h->bt_loc_cap * sizeof(int);
+        const size_t held = 2 * h->bt.mat.size() * sizeof(unsigned long long) + h->bt.vec.size() * (1 + 5 * sizeof(int)) + h->bt.loc.size() * sizeof(int);
         budget = (mem_free + held) / 4;
         if (h->batch_budget) budget = std::min(budget, h->batch_budget);
     }
@@ -2989,51 +2938,24 @@ extern "C" int ipc_run_batch(ipc_engine_t* h, int n_runs, const int* run_offsets
     const size_t need_loc = need_runs * (size_t)N, need_memb = (size_t)N * mw;
     hipStream_t st = h->own_stream;
     if (int rc = matrix_mode_enter(h, st)) return rc;
-    if (need_mat > h->bt_mat_cap) {
-        h->bt_mat_cap = 0;                               // (until both are there: a failure part way comes here again)
-        h->d_bt_upper.reset(); h->d_bt_bits.reset();
-        HIPCHK(h->d_bt_upper.alloc(need_mat));
-        HIPCHK(h->d_bt_bits.alloc(need_mat));
-        h->bt_mat_cap = need_mat;
-    }
-    if (need_vec > h->bt_vec_cap) {
-        h->bt_vec_cap = 0;
-        h->d_bt_acc.reset(); h->d_bt_vec.reset();
-        HIPCHK(h->d_bt_acc.alloc(need_vec));
-        HIPCHK(h->d_bt_vec.alloc(5 * need_vec));
-        h->bt_vec_cap = need_vec;
-    }
-    if (need_loc > h->bt_loc_cap) {
-        h->bt_loc_cap = 0;
-        HIPCHK(h->d_bt_loc.alloc(need_loc));
-        h->bt_loc_cap = need_loc;
-    }
-    if (need_runs > h->bt_runs_cap) {
-        h->bt_runs_cap = 0;
-        HIPCHK(h->d_bt_runs.alloc(need_runs));
-        h->bt_runs_cap = need_runs;
-    }
-    if (need_memb > h->bt_memb_cap) {
-        h->bt_memb_cap = 0;
-        HIPCHK(h->d_bt_memb.alloc(need_memb));
-        if (!h->d_bt_sep) HIPCHK(h->d_bt_sep.alloc(1));
-        h->bt_memb_cap = need_memb;
-    }
+    auto& b = h->bt;
+    HIPCHK(b.mat.grow(need_mat, sized(b.d_upper, need_mat), sized(b.d_bits, need_mat)));
+    HIPCHK(b.vec.grow(need_vec, sized(b.d_acc, need_vec), sized(b.d_vec, 5 * need_vec)));
+    HIPCHK(b.loc.grow(need_loc, sized(b.d_loc, need_loc)));
+    HIPCHK(b.runs.grow(need_runs, sized(b.d_runs, need_runs)));
+    HIPCHK(b.memb.grow(need_memb, sized(b.d_memb, need_memb)));
+    if (!b.d_sep) HIPCHK(b.d_sep.alloc(1));
     // the pinned staging, in 8-byte words: the membership words, later a chunk's descriptors, orders, members and maps
     const size_t stage_runs = (need_runs * sizeof(BatchRun) + 7) / 8, stage_vec = (need_vec * sizeof(int) + 7) / 8;
     const size_t need_stage = std::max(need_memb, stage_runs + 2 * stage_vec + (need_loc * sizeof(int) + 7) / 8);
-    if (need_stage > h->bt_stage_cap) {
-        h->bt_stage_cap = 0;
-        HIPCHK(h->h_bt_stage.alloc(need_stage));
-        h->bt_stage_cap = need_stage;
-    }
+    HIPCHK(b.stage.grow(need_stage, sized(b.h_stage, need_stage)));
     // membership words
-    unsigned long long* memb = h->h_bt_stage;
+    unsigned long long* memb = h->bt.h_stage;
     std::fill(memb, memb + need_memb, 0ull);
     for (int r = 0; r < R; ++r)
         for (int k = run_offsets[r]; k < run_offsets[r + 1]; ++k) memb[(size_t)members[k] * mw + (r >> 6)] |= 1ull << (r & 63);
-    HIPCHK(hipMemcpyAsync(h->d_bt_memb, memb, sizeof(unsigned long long) * need_memb, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(h->d_bt_sep, 0, sizeof(unsigned long long), st));
+    HIPCHK(hipMemcpyAsync(h->bt.d_memb, memb, sizeof(unsigned long long) * need_memb, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(h->bt.d_sep, 0, sizeof(unsigned long long), st));
     // The cells some run needs, into d_cells & co. (the cached plan of the batch path is gone: plan_cells), in the row order of
     // a one-rank step; then the engine's own solve -- borderline literal re-solves and Levenberg retries once per shared cell.
     if (int rc = ensure_row_map(h, 1)) return rc;
@@ -3043,7 +2965,7 @@ extern "C" int ipc_run_batch(ipc_engine_t* h, int n_runs, const int* run_offsets
         const dim3 pgrid((N + 255) / 256, std::max(1, std::min(N, 2048))), pblock(256);
         if (int rc = plan_cells(h, st, pl, 0, [&](int2* cells, int fill) {
                 hipLaunchKernelGGL(k_plan_batch, pgrid, pblock, 0, st, N, (const int*)h->d_lo, (const int*)h->d_hi, (const int*)h->d_rowperm, N, bc,
-                                   h->d_counters, (const unsigned*)h->d_offsets, cells, fill, (const unsigned long long*)h->d_bt_memb, mw, h->d_bt_sep);
+                                   h->d_counters, (const unsigned*)h->d_offsets, cells, fill, (const unsigned long long*)h->bt.d_memb, mw, h->bt.d_sep);
             })) return rc;
     }
     const size_t total = pl.total;
@@ -3053,7 +2975,7 @@ extern "C" int ipc_run_batch(ipc_engine_t* h, int n_runs, const int* run_offsets
     rep.long_cells = h->last_long_cells; rep.damped_cells = h->last_lm_cells; rep.literal_cells = h->last_literal_cells;
     {
         unsigned long long sep = 0;
-        HIPCHK(hipMemcpyAsync(&sep, h->d_bt_sep, sizeof sep, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(&sep, h->bt.d_sep, sizeof sep, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));                // (also: the membership words have left the staging buffer)
         rep.cells_separate = (long long)sep;
     }
@@ -3062,10 +2984,10 @@ extern "C" int ipc_run_batch(ipc_engine_t* h, int n_runs, const int* run_offsets
     for (int q = 0; q < n_chunks; ++q) {
         const int c0 = chunk_first[q], n = chunk_first[q + 1] - c0, v0 = run_offsets[c0];
         const size_t nvec = (size_t)(run_offsets[c0 + n] - v0);
-        BatchRun* s_runs = (BatchRun*)(unsigned long long*)h->h_bt_stage;
-        int* s_order = (int*)((unsigned long long*)h->h_bt_stage + stage_runs);
-        int* s_memb = (int*)((unsigned long long*)h->h_bt_stage + stage_runs + stage_vec);
-        int* s_loc = (int*)((unsigned long long*)h->h_bt_stage + stage_runs + 2 * stage_vec);
+        BatchRun* s_runs = (BatchRun*)(unsigned long long*)h->bt.h_stage;
+        int* s_order = (int*)((unsigned long long*)h->bt.h_stage + stage_runs);
+        int* s_memb = (int*)((unsigned long long*)h->bt.h_stage + stage_runs + stage_vec);
+        int* s_loc = (int*)((unsigned long long*)h->bt.h_stage + stage_runs + 2 * stage_vec);
         size_t mat = 0;
         int max_n = 0;
         for (int rc = 0; rc < n; ++rc) {
@@ -3080,28 +3002,28 @@ extern "C" int ipc_run_batch(ipc_engine_t* h, int n_runs, const int* run_offsets
             int pos = 0;
             for (int p = 0; p < N; ++p) { const int l = loc[h->order[p]]; if (l >= 0) s_order[voff + pos++] = l; }
         }
-        int* d_live = h->d_bt_vec; int* d_lo_r = d_live + h->bt_vec_cap; int* d_hi_r = d_lo_r + h->bt_vec_cap;
-        int* d_order_r = d_hi_r + h->bt_vec_cap; int* d_memb_r = d_order_r + h->bt_vec_cap;
-        HIPCHK(hipMemcpyAsync(h->d_bt_runs, s_runs, sizeof(BatchRun) * n, hipMemcpyHostToDevice, st));
+        int* d_live = b.vec.part(b.d_vec, 0); int* d_lo_r = b.vec.part(b.d_vec, 1); int* d_hi_r = b.vec.part(b.d_vec, 2);
+        int* d_order_r = b.vec.part(b.d_vec, 3); int* d_memb_r = b.vec.part(b.d_vec, 4);
+        HIPCHK(hipMemcpyAsync(h->bt.d_runs, s_runs, sizeof(BatchRun) * n, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_order_r, s_order, sizeof(int) * nvec, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_memb_r, s_memb, sizeof(int) * nvec, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(h->d_bt_loc, s_loc, sizeof(int) * (size_t)n * N, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemsetAsync(h->d_bt_upper, 0, sizeof(unsigned long long) * mat, st));
+        HIPCHK(hipMemcpyAsync(h->bt.d_loc, s_loc, sizeof(int) * (size_t)n * N, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(h->bt.d_upper, 0, sizeof(unsigned long long) * mat, st));
         const int max_words = (max_n + 63) / 64, max_tiles = ((max_n - 1) >> 6) + 1;
-        hipLaunchKernelGGL(k_batch_gather, dim3((max_n + 255) / 256, n), dim3(256), 0, st, (const BatchRun*)h->d_bt_runs, (const int*)d_memb_r,
+        hipLaunchKernelGGL(k_batch_gather, dim3((max_n + 255) / 256, n), dim3(256), 0, st, (const BatchRun*)h->bt.d_runs, (const int*)d_memb_r,
                            (const int*)h->d_lo, (const int*)h->d_hi, d_lo_r, d_hi_r);
         if (total)
-            hipLaunchKernelGGL(k_batch_scatter, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total, (const int2*)h->d_cells,
-                               (const double*)h->d_chi, h->prm.fast_reject_th, h->prm.slow_reject_th, (const unsigned long long*)h->d_bt_memb, mw, c0, n,
-                               N, (const BatchRun*)h->d_bt_runs, (const int*)h->d_bt_loc, h->d_bt_upper);
-        hipLaunchKernelGGL(k_batch_assemble, dim3(max_words, std::min((max_tiles + 3) / 4, 1024), n), dim3(256), 0, st, (const BatchRun*)h->d_bt_runs,
-                           (const int*)d_lo_r, (const int*)d_hi_r, (const unsigned long long*)h->d_bt_upper, h->d_bt_bits);
-        hipLaunchKernelGGL(k_batch_set_max, dim3(n), dim3(1024), sizeof(unsigned long long) * max_words, st, (const BatchRun*)h->d_bt_runs,
-                           (const int*)d_order_r, (const unsigned long long*)h->d_bt_bits, h->d_bt_acc, d_live);
+            hipLaunchKernelGGL(k_batch_scatter, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (int)total, (const int2*)h->cells.d_cells,
+                               (const double*)h->cells.d_chi, h->prm.fast_reject_th, h->prm.slow_reject_th, (const unsigned long long*)h->bt.d_memb, mw, c0, n,
+                               N, (const BatchRun*)h->bt.d_runs, (const int*)h->bt.d_loc, h->bt.d_upper);
+        hipLaunchKernelGGL(k_batch_assemble, dim3(max_words, std::min((max_tiles + 3) / 4, 1024), n), dim3(256), 0, st, (const BatchRun*)h->bt.d_runs,
+                           (const int*)d_lo_r, (const int*)d_hi_r, (const unsigned long long*)h->bt.d_upper, h->bt.d_bits);
+        hipLaunchKernelGGL(k_batch_set_max, dim3(n), dim3(1024), sizeof(unsigned long long) * max_words, st, (const BatchRun*)h->bt.d_runs,
+                           (const int*)d_order_r, (const unsigned long long*)h->bt.d_bits, h->bt.d_acc, d_live);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));                // (the staging buffer is free for the next chunk when this returns)
-        if (bits_out) HIPCHK(hipMemcpy(bits_out + bits_done, h->d_bt_bits, sizeof(uint64_t) * mat, hipMemcpyDeviceToHost));
-        if (accepted_out) HIPCHK(hipMemcpy(accepted_out + v0, h->d_bt_acc, nvec, hipMemcpyDeviceToHost));
+        if (bits_out) HIPCHK(hipMemcpy(bits_out + bits_done, h->bt.d_bits, sizeof(uint64_t) * mat, hipMemcpyDeviceToHost));
+        if (accepted_out) HIPCHK(hipMemcpy(accepted_out + v0, h->bt.d_acc, nvec, hipMemcpyDeviceToHost));
         bits_done += mat;
         ++rep.chunks;
     }
@@ -3127,10 +3049,10 @@ extern "C" int ipc_cell_info(ipc_engine_t* h, ipc_cell_info_t* out, int capacity
     std::vector<double> chi(n), tot(n);
     std::vector<int4> meta(n);
     const bool sw = h->info_from_sweep;                  // after ipc_run_sweep: the first-pass records it holds
-    HIPCHK(hipMemcpy(cells.data(), sw ? h->d_sw_cells : h->d_cells, sizeof(int2) * n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(chi.data(), sw ? h->d_sw_chi : h->d_chi, sizeof(double) * n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(tot.data(), sw ? h->d_sw_chitot : h->d_chitot, sizeof(double) * n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(meta.data(), sw ? h->d_sw_meta : h->d_meta, sizeof(int4) * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(cells.data(), sw ? h->sw.d_cells : h->cells.d_cells, sizeof(int2) * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(chi.data(), sw ? h->sw.d_chi : h->cells.d_chi, sizeof(double) * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(tot.data(), sw ? h->sw.d_chitot : h->cells.d_chitot, sizeof(double) * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(meta.data(), sw ? h->sw.d_meta : h->cells.d_meta, sizeof(int4) * n, hipMemcpyDeviceToHost));
     for (int c = 0; c < n; ++c) {
         ipc_cell_info_t& o = out[c];
         o.i = cells[c].x; o.j = cells[c].y;
@@ -3167,7 +3089,7 @@ extern "C" int ipc_solve_report(ipc_engine_t* h, ipc_solve_report_t* out)
     HIPCHK(hipMemsetAsync(h->d_counters, 0, sizeof(unsigned) * 3, h->own_stream));
     const bool sw = h->info_from_sweep;                  // after ipc_run_sweep: the first-pass records it holds
     hipLaunchKernelGGL(k_report, dim3((h->last_cells + 255) / 256), dim3(256), 0, h->own_stream, h->last_cells,
-                       (const int4*)(sw ? h->d_sw_meta : h->d_meta), (const double*)(sw ? h->d_sw_chi : h->d_chi), h->d_counters);
+                       (const int4*)(sw ? h->sw.d_meta : h->cells.d_meta), (const double*)(sw ? h->sw.d_chi : h->cells.d_chi), h->d_counters);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(host, h->d_counters, sizeof host, hipMemcpyDeviceToHost, h->own_stream));
     HIPCHK(hipStreamSynchronize(h->own_stream));
@@ -4783,19 +4705,13 @@ extern "C" int ipc_run_set_only(ipc_engine_t* h, uint8_t* accepted_out, int* sol
     if (!h) return fail(IPC_ERR_ARG, "ipc_run_set_only: NULL handle");
     if (h->N <= 0) return fail(IPC_ERR_STATE, "ipc_run_set_only: no candidates set");
     HIPCHK(hipSetDevice(h->device));
-    const int N = h->N, words = (N + 63) / 64;
-    const size_t need = (size_t)N * words;
-    if (int rc = ensure_run_scratch(h, N, need)) return rc;
-    int rc = solve_rows_impl(h, 0, 1, h->d_upper, h->own_stream, 1);
-    const int diag_cells = h->last_cells;
-    if (!rc) rc = solve_rows_impl(h, 0, 1, h->d_upper, h->own_stream, 2);
-    if (!rc) rc = ipc_assemble_matrix(h, h->d_upper, 1, h->d_bits, h->own_stream);
-    if (!rc) rc = ipc_set_max(h, h->d_bits, h->d_acc, h->own_stream);
-    if (rc) return rc;
+    int diag_cells = 0;
+    if (int rc = ensure_run_scratch(h)) return rc;
+    if (int rc = run_matrix(h, &diag_cells)) return rc;
+    if (int rc = ipc_set_max(h, h->run.d_bits, h->run.d_acc, h->own_stream)) return rc;
     HIPCHK(hipStreamSynchronize(h->own_stream));
     if (solved_cells_out) *solved_cells_out = diag_cells + h->last_cells;
-    if (accepted_out) HIPCHK(hipMemcpy(accepted_out, h->d_acc, (size_t)N, hipMemcpyDeviceToHost));
-    return IPC_OK;
+    return run_copy_out(h, nullptr, accepted_out, h->run.d_acc);
 }
 
 // Matrix mode over several GPUs of one node from ONE process (the C++ testers' IPC_AMD_DEVICES): engines[r] hold the
@@ -4816,9 +4732,9 @@ extern "C" int ipc_run_sharded(ipc_engine_t** engines, int n_engines, uint64_t* 
     if (h0->N <= 0) return fail(IPC_ERR_STATE, "ipc_run_sharded: no candidates set");
     if (n_engines == 1) return ipc_run(h0, bits_out, accepted_out);
     const int N = h0->N, words = (N + 63) / 64, world = n_engines, rpr = ipc_rows_per_rank(N, world);
-    const size_t shard = (size_t)rpr * words, need = (size_t)N * words;
+    const size_t shard = (size_t)rpr * words;
     HIPCHK(hipSetDevice(h0->device));
-    if (int rc = ensure_run_scratch(h0, N, need)) return rc;
+    if (int rc = ensure_run_scratch(h0)) return rc;
     DevBuf<uint64_t> d_gathered;
     HIPCHK(d_gathered.alloc(shard * world));
     std::vector<int> rcs(world, IPC_OK);
@@ -4846,13 +4762,11 @@ extern "C" int ipc_run_sharded(ipc_engine_t** engines, int n_engines, uint64_t* 
     HIPCHK(hipSetDevice(h0->device));
     for (int r = 0; r < world; ++r)
         if (rcs[r]) return fail((ipc_status)rcs[r], "ipc_run_sharded: rank %d: %s", r, errs[r].c_str());
-    int rc = ipc_assemble_matrix(h0, d_gathered, world, h0->d_bits, h0->own_stream);
-    if (!rc) rc = ipc_set_max(h0, h0->d_bits, h0->d_acc, h0->own_stream);
+    int rc = ipc_assemble_matrix(h0, d_gathered, world, h0->run.d_bits, h0->own_stream);
+    if (!rc) rc = ipc_set_max(h0, h0->run.d_bits, h0->run.d_acc, h0->own_stream);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(h0->own_stream));
     d_gathered.reset();
-    if (bits_out) HIPCHK(hipMemcpy(bits_out, h0->d_bits, sizeof(uint64_t) * need, hipMemcpyDeviceToHost));
-    if (accepted_out) HIPCHK(hipMemcpy(accepted_out, h0->d_acc, (size_t)N, hipMemcpyDeviceToHost));
-    return IPC_OK;
+    return run_copy_out(h0, bits_out, accepted_out, h0->run.d_acc);
 }
 

@@ -80,4 +80,42 @@ struct Event : Owned<ihipEvent_t, hipEventDestroy, g_live_events> {
     hipError_t create(unsigned flags = hipEventDefault) { return acquire([&](hipEvent_t* ev) { return hipEventCreateWithFlags(ev, flags); }); }
 };
 
+// Scratch buffers that grow together, and the capacity they were sized for: the capacity stands next to its members in one
+// struct and every growth names them all,
+//     HIPCHK(g.cap.grow(need, sized(g.a, need), sized(g.b, need + 1)));
+// Nothing is allocated or freed while need <= capacity.  A growth releases every member before it allocates the first (the
+// contents are scratch and are not kept) and the capacity reads 0 until the last member is there: after a failure part way the
+// next call grows again from scratch.  Sub-arrays of one member are cut at the capacity (part), never at the need of a call.
+// A member is anything with reset() and alloc(count) -> hipError_t -- which a ScratchCap is itself: a group with a second
+// capacity, in another unit, lists that one as its last member.
+template <class Buf>
+struct Sized { Buf& buf; size_t count; };
+template <class Buf>
+Sized<Buf> sized(Buf& buf, size_t count) { return {buf, count}; }
+
+class ScratchCap {
+public:
+    size_t size() const { return cap_; }
+    template <class... Buf>
+    hipError_t grow(size_t need, Sized<Buf>... members) { return need <= cap_ ? hipSuccess : regrow(need, members...); }
+    template <class... Buf>
+    hipError_t regrow(size_t cap, Sized<Buf>... members)           // whatever it holds: for a caller with a growth rule of its own
+    {
+        cap_ = 0;
+        (members.buf.reset(), ...);
+        hipError_t e = hipSuccess;
+        (void)(((e = members.buf.alloc(members.count)) == hipSuccess) && ...);
+        if (e == hipSuccess) cap_ = cap;
+        return e;
+    }
+    template <class Buf>
+    auto part(const Buf& buf, size_t k) const { return buf.get() + k * cap_; }     // the k-th sub-array of `buf`, [parts][capacity]
+
+    void reset() { cap_ = 0; }
+    hipError_t alloc(size_t count) { cap_ = count; return hipSuccess; }
+
+private:
+    size_t cap_ = 0;
+};
+
 }  // namespace ipc
