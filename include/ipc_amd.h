@@ -423,6 +423,7 @@ int ipc_run_exact(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accepted_out, ui
  * Three further entry points of the library, declared in a header of their own beside this one, which it needs for the
  * handle and the online report and which includes it here (inside the extern "C" block, where there is one). */
 #include "ipc_amd_online_exact.h"
+#include "ipc_amd_lazy_sd.h"
 
 /* Diagnostics of the last ipc_solve_rows(), ipc_run_online(), ipc_run_sweep() or ipc_run_batch(): number of solved cells, and their records. */
 int ipc_cell_count(ipc_engine_t* h, int* n_cells);

@@ -42,6 +42,8 @@ SYMBOLS = [
 ]
 # every symbol include/ipc_amd_online_exact.h declares (checked by tests/test_exact_resume_cpu.py)
 SYMBOLS_ONLINE_EXACT = ["ipc_set_max_exact_resume", "ipc_run_online_exact", "ipc_online_exact_state"]
+# the symbol include/ipc_amd_lazy_sd.h declares
+SYMBOLS_LAZY_SD = ["ipc_se2_lazy_sd_launches"]
 
 
 class Params(C.Structure):
@@ -168,6 +170,8 @@ def load():
     lib.ipc_solve_report.argtypes = [vp, C.POINTER(SolveReport)]
     lib.ipc_solver_time_ms.argtypes = [vp, C.POINTER(dp), C.POINTER(ip)]
     lib.ipc_synchronize.argtypes = [vp]
+    if hasattr(lib, "ipc_se2_lazy_sd_launches"):       # (an A/B library of an older build, IPC_AMD_LIB / tools/ab_libs.py, lacks it)
+        lib.ipc_se2_lazy_sd_launches.argtypes = [vp, C.POINTER(C.c_longlong)]
     lib.ipc_incremental_reset.argtypes = [vp]
     lib.ipc_incremental_prepare.argtypes = [vp]
     lib.ipc_agreement_check.argtypes = [vp, ip, C.POINTER(ip), C.POINTER(CheckInfo)]

@@ -367,6 +367,12 @@ class IPC:
         capi.check(self.lib.ipc_solve_report(self.h, C.byref(r)))
         return {k: getattr(r, k) for k, _ in capi.SolveReport._fields_}
 
+    def lazy_sd_launches(self):
+        """Launches of a lazy steepest-descent SE2 cell kernel since this engine was created (0 with IPC_SE2_LAZY_SD=0)."""
+        n = C.c_longlong(0)
+        capi.check(self.lib.ipc_se2_lazy_sd_launches(self.h, C.byref(n)))
+        return n.value
+
     def solver_time_ms(self):
         ms, nl = C.c_double(0), C.c_int(0)
         capi.check(self.lib.ipc_solver_time_ms(self.h, C.byref(ms), C.byref(nl)))

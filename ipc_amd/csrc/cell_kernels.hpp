@@ -1,5 +1,5 @@
 // Launch interface of the cell-solver kernels.  The kernels are heavily templated, so they live
-// in their own translation units (se2_block.hip, se2_wave.hip, se2_wave_kt.hip, se2_pair.hip, se2_pair_kt.hip, se2_quad.hip, se3_block.hip) that are compiled
+// in their own translation units (se2_block.hip, se2_wave.hip, se2_wave_kt.hip, se2_wave_lz.hip, se2_pair.hip, se2_pair_kt.hip, se2_pair_lz.hip, se2_quad.hip, se3_block.hip) that are compiled
 // in parallel and linked into libipc_amd.so; engine.hip only sees these prototypes.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -93,6 +93,20 @@ static const int kPairKtM[] = {7, 9, 11};
 constexpr int kNumPairKtM = sizeof(kPairKtM) / sizeof(kPairKtM[0]);
 constexpr int kPairKtVariantBase = 600;
 hipError_t launch_se2_pair_kt(int nl, int M, int n, hipStream_t st, const Se2View& P, const int2* cells,
+                              SolveParams prm, CellOut out, unsigned* counter, int n_cu);
+
+// ---- lazy steepest-descent wave and pair kernels (SE2, se2_wave_lz.hip / se2_pair_lz.hip; LAZY_SD of se2_wave_solve):
+// the same cells, capacities and results, bit for bit, as the kernel the default policy names for that M (kept trial up to
+// M = kLazyKeepTrialMaxM, re-sweep beyond); b^T H b, alpha and |h_sd| are formed only in the iterations whose trial
+// loop reads them.  No policy token: the engine serves a bin of that kernel with this one (IPC_SE2_LAZY_SD, engine.hip) ----
+constexpr int kLazyKeepTrialMaxM = 9;
+static const int kWaveLzM[] = {5, 7, 9, 11, 13};
+constexpr int kNumWaveLzM = sizeof(kWaveLzM) / sizeof(kWaveLzM[0]);
+hipError_t launch_se2_wave_lz(int nl, int M, int n, hipStream_t st, const Se2View& P, const int2* cells,
+                              SolveParams prm, CellOut out, unsigned* counter, int n_cu);
+static const int kPairLzM[] = {7, 9, 11};
+constexpr int kNumPairLzM = sizeof(kPairLzM) / sizeof(kPairLzM[0]);
+hipError_t launch_se2_pair_lz(int nl, int M, int n, hipStream_t st, const Se2View& P, const int2* cells,
                               SolveParams prm, CellOut out, unsigned* counter, int n_cu);
 
 }  // namespace ipc

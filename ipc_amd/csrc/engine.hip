@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdarg>
 #include <cstdlib>
 #include <utility>
@@ -607,10 +608,43 @@ struct BinPlan {
     // cells finish sooner), and the cell count below which it is used
     int latency_variant[kMaxBins];
     int latency_below[kMaxBins];
+    // SE2: the bin's kernel is served by its lazy steepest-descent form (same cells, same bits; lazy_sd_serves below)
+    bool lazy_sd[kMaxBins];
 };
 // kwM / kpM where the kept-trial kernel passed its static and its measured gate: not at M = 11, whose
 // kept-trial kernels spill to scratch and run slower than w11 / p11
 static const char* kDefaultPolicy = "w1,w3,kw5,kw7,kw9,w11,w13,kp7,kp9,p11,q7,q9,q11,q13,16x4,16x8,16x16";
+// The lazy steepest-descent kernels (se2_wave_lz.hip / se2_pair_lz.hip, LAZY_SD of se2_wave_solve) are not variants of
+// their own: each computes, bit for bit, what one kernel of the default policy computes, so it has no token, no capacity
+// and no place in a policy string -- a bin whose variant is that kernel is served by the lazy one.  IPC_SE2_LAZY_SD=0
+// (read with the policy) switches the substitution off: every token then launches the kernel it names, which is the A/B
+// partner inside one library; =2 substitutes every M that has a lazy kernel, listed below or not (the bitwise test and
+// the per-bin gate runs reach the unlisted ones that way).  Only the M listed here are substituted by default: the
+// kernels that passed the static gate (tests/test_se2_lazy_sd_loop_mix.py) and the measured one
+// (profiles/se2_lazy_sd_c2_kernel_gate.txt).
+// Every one of the eight is faster in its bin on the MI355X (-2.4 to -10.9 %); lw9, lp7 and lp9 are held back by the static
+// gate alone (two spilled vector registers, or two spilled scalar registers, more than the counterpart in one or two of
+// their four instantiations) and lw13 by its scratch: DESIGN.md 8 has the figures.
+static const int kLazySdWaveM[] = {5, 7, 11};            // for kw5, kw7, w11     (not 9: kw9, not 13: w13)
+static const int kLazySdPairM[] = {11};                  // for p11               (not 7, 9: kp7, kp9)
+static bool lazy_sd_serves(int variant, bool every)    // every: any M that has a lazy kernel (IPC_SE2_LAZY_SD=2, tests and gate runs)
+{
+    bool wave = false, pair = false;
+    int m = 0;
+    if (variant >= kPairKtVariantBase) { pair = true; m = variant - kPairKtVariantBase; if (m > kLazyKeepTrialMaxM) return false; }
+    else if (variant >= kWaveKtVariantBase) { wave = true; m = variant - kWaveKtVariantBase; if (m > kLazyKeepTrialMaxM) return false; }
+    else if (variant >= kQuadVariantBase) return false;
+    else if (variant >= kPairVariantBase) { pair = true; m = variant - kPairVariantBase; if (m <= kLazyKeepTrialMaxM) return false; }
+    else if (variant >= kWaveVariantBase) { wave = true; m = variant - kWaveVariantBase; if (m <= kLazyKeepTrialMaxM) return false; }
+    if (every) {
+        if (wave) for (int k : kWaveLzM) if (k == m) return true;
+        if (pair) for (int k : kPairLzM) if (k == m) return true;
+        return false;
+    }
+    if (wave) for (int k : kLazySdWaveM) if (k == m) return true;
+    if (pair) for (int k : kLazySdPairM) if (k == m) return true;
+    return false;
+}
 // engine streams + the caller's stream = the runtime's four hardware queues for SE2; the long SE3
 // launches gain a little from a fourth engine stream
 static const int kDefaultSideStreams2 = 7, kDefaultSideStreams3 = 7;      // (round 5: 2 / 3 until the side streams came from the process pool -- at 8 ranks a shard's bins hold fewer cells than the GPU has CUs and only concurrent launches fill it: C2 emulated 6.53x -> 7.07x, one rank unchanged)
@@ -668,6 +702,13 @@ static bool make_plan(BinPlan& bp, int dim, std::string& err)
         bp.variant[b] = b < bp.caps.n ? items[b].second : -1;
         bp.latency_variant[b] = -1;
         bp.latency_below[b] = 0;
+        bp.lazy_sd[b] = false;
+    }
+    if (dim == 2) {
+        const char* lz = getenv("IPC_SE2_LAZY_SD");
+        if (lz && *lz && strcmp(lz, "0") != 0 && strcmp(lz, "1") != 0 && strcmp(lz, "2") != 0) { err = "IPC_SE2_LAZY_SD: 0, 1 or 2"; return false; }
+        const bool lazy_on = !(lz && *lz == '0'), every = lz && *lz == '2';
+        for (int b = 0; b < bp.caps.n; ++b) bp.lazy_sd[b] = lazy_on && lazy_sd_serves(bp.variant[b], every);
     }
     if (dim == 3) {
         const char* lenv = getenv("IPC_SE3_LATENCY_POLICY");
@@ -772,6 +813,7 @@ struct ipc_engine {
     DevBuf<unsigned> d_slot_off;                       // [slots + 1] first cell of each (loop count, bin) slot
     DevBuf<int> d_recount; PinnedBuf<int> h_recount;      // [slots] borderline cells per slot, then the failed-cell count; pinned copy
     int last_cells = 0, last_long_cells = 0;
+    mutable std::atomic<long long> lazy_sd_launches{0};   // launches of a lazy steepest-descent kernel (ipc_se2_lazy_sd_launches)
     Event ev0, ev1; bool ev_valid = false; int last_launches = 0;
     // side streams: the bin launches of one solve are spread over them so that the tail of one
     // launch (a few cells that run to the iteration cap) overlaps the next bins
@@ -1938,6 +1980,13 @@ struct SlotLauncher {
     {
         int var = h->plan.variant[b];
         if (h->plan.latency_variant[b] >= 0 && n < h->plan.latency_below[b] * h->n_cu) var = h->plan.latency_variant[b];
+        if (h->dim == 2 && var == h->plan.variant[b] && h->plan.lazy_sd[b]) {
+            h->lazy_sd_launches.fetch_add(1, std::memory_order_relaxed);
+            const bool pair = var >= kPairKtVariantBase || (var < kWaveKtVariantBase && var >= kPairVariantBase);
+            const int m = var % 100;
+            return pair ? launch_se2_pair_lz(nl, m, n, ls, P, cells, sp, out, ctr, h->n_cu)
+                        : launch_se2_wave_lz(nl, m, n, ls, P, cells, sp, out, ctr, h->n_cu);
+        }
         if (h->dim == 2)
             return var >= kPairKtVariantBase ? launch_se2_pair_kt(nl, var - kPairKtVariantBase, n, ls, P, cells, sp, out, ctr, h->n_cu)
                    : var >= kWaveKtVariantBase ? launch_se2_wave_kt(nl, var - kWaveKtVariantBase, n, ls, P, cells, sp, out, ctr, h->n_cu)
@@ -3111,6 +3160,13 @@ extern "C" int ipc_solver_time_ms(ipc_engine_t* h, double* ms, int* launches)
     HIPCHK(hipEventElapsedTime(&t, h->ev0, h->ev1));
     *ms = t;
     if (launches) *launches = h->last_launches;
+    return IPC_OK;
+}
+
+extern "C" int ipc_se2_lazy_sd_launches(ipc_engine_t* h, long long* launches)
+{
+    if (!h || !launches) return fail(IPC_ERR_ARG, "ipc_se2_lazy_sd_launches: NULL argument");
+    *launches = h->lazy_sd_launches.load(std::memory_order_relaxed);
     return IPC_OK;
 }
 

@@ -13,10 +13,13 @@ constexpr int kWavesPerGroup = 4;
 #endif
 constexpr int kLdsBudget = IPC_LDS_BUDGET;
 
-// Two kernel templates, one text (se2_group_kernel_def.hpp): se2_group_kernel re-sweeps an accepted trial to commit it;
-// se2_group_kernel_kt (kept trial) reads it back from the accumulator registers where the trial sweep parked it.
+// Three kernel templates, one text (se2_group_kernel_def.hpp): se2_group_kernel re-sweeps an accepted trial to commit it;
+// se2_group_kernel_kt (kept trial) reads it back from the accumulator registers where the trial sweep parked it;
+// se2_group_kernel_lz (LAZY_SD of se2_wave_solve) forms the steepest-descent terms only where a trial reads them and
+// commits as the default policy's kernel of that M does (kept trial up to M = 9, re-sweep beyond).
 #define IPC_GROUP_KERNEL_NAME se2_group_kernel
 #define IPC_GROUP_KEEP_TRIAL false
+#define IPC_GROUP_LAZY_SD false
 #include "se2_group_kernel_def.hpp"
 #undef IPC_GROUP_KERNEL_NAME
 #undef IPC_GROUP_KEEP_TRIAL
@@ -25,16 +28,25 @@ constexpr int kLdsBudget = IPC_LDS_BUDGET;
 #include "se2_group_kernel_def.hpp"
 #undef IPC_GROUP_KERNEL_NAME
 #undef IPC_GROUP_KEEP_TRIAL
+#undef IPC_GROUP_LAZY_SD
+#define IPC_GROUP_KERNEL_NAME se2_group_kernel_lz
+#define IPC_GROUP_KEEP_TRIAL (M <= kLazyKeepTrialMaxM)
+#define IPC_GROUP_LAZY_SD true
+#include "se2_group_kernel_def.hpp"
+#undef IPC_GROUP_KERNEL_NAME
+#undef IPC_GROUP_KEEP_TRIAL
+#undef IPC_GROUP_LAZY_SD
 
 // (only the chosen template is instantiated: a translation unit emits the kernels it launches and no others)
-template <int W, int M, int NL, bool STAGED, bool KEEP_TRIAL>
+template <int W, int M, int NL, bool STAGED, bool KEEP_TRIAL, bool LAZY_SD>
 constexpr auto se2_group_kernel_of()
 {
-    if constexpr (KEEP_TRIAL) return &se2_group_kernel_kt<W, M, NL, STAGED>;
+    if constexpr (LAZY_SD) return &se2_group_kernel_lz<W, M, NL, STAGED>;
+    else if constexpr (KEEP_TRIAL) return &se2_group_kernel_kt<W, M, NL, STAGED>;
     else return &se2_group_kernel<W, M, NL, STAGED>;
 }
 
-template <int W, int M, int NL, bool KEEP_TRIAL = false>
+template <int W, int M, int NL, bool KEEP_TRIAL = false, bool LAZY_SD = false>
 static hipError_t launch_group(int n, hipStream_t st, const Se2View& P, const int2* cells, SolveParams prm, CellOut out,
                               unsigned* counter, int n_cu)
 {
@@ -45,12 +57,12 @@ static hipError_t launch_group(int n, hipStream_t st, const Se2View& P, const in
     const size_t staged = scratch + sizeof(double) * (size_t)F_SG * wstride;
     const int groups = std::max(1, std::min(n_cu, (n + kPairs - 1) / kPairs));
     if (staged <= (size_t)kLdsBudget) {
-        auto k = se2_group_kernel_of<W, M, NL, true, KEEP_TRIAL>();
+        auto k = se2_group_kernel_of<W, M, NL, true, KEEP_TRIAL, LAZY_SD>();
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)staged);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k, dim3(groups), dim3(64 * kWavesPerGroup), staged, st, P, cells, n, counter, prm, out, 0, E, wstride);
     } else {
-        auto k = se2_group_kernel_of<W, M, NL, false, KEEP_TRIAL>();
+        auto k = se2_group_kernel_of<W, M, NL, false, KEEP_TRIAL, LAZY_SD>();
         hipLaunchKernelGGL(k, dim3(groups), dim3(64 * kWavesPerGroup), scratch, st, P, cells, n, counter, prm, out, 0, E, wstride);
     }
     return hipGetLastError();

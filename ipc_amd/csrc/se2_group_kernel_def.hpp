@@ -3,7 +3,8 @@
 //   IPC_GROUP_KERNEL_NAME   name of the __global__ template
 //   IPC_GROUP_KEEP_TRIAL    KEEP_TRIAL of se2_wave_solve: false, an accepted trial is re-swept to commit; true, it is
 //                           read back from the accumulator registers where the trial sweep parked it
-// (no include guard).  One text for both kernels, and no function between the kernel and se2_wave_solve: routed through
+//   IPC_GROUP_LAZY_SD       LAZY_SD of se2_wave_solve: true, the steepest-descent terms are formed only where a trial reads them
+// (no include guard).  One text for all kernels, and no function between the kernel and se2_wave_solve: routed through
 // a shared, force-inlined body the instantiations of se2_group_kernel compile to different code (registers, spills, loop
 // layout) than they did as a kernel of their own, and their loop bodies are held to committed tables instruction by
 // instruction (tests/test_se2_loop_mix.py, tests/test_se2_keep_errors_loop_mix.py).
@@ -63,8 +64,8 @@ __global__ __launch_bounds__(64 * kWavesPerGroup, 1) void IPC_GROUP_KERNEL_NAME(
         const int base = NL == 1 ? prm.fast_iter : prm.slow_iter;
         const int iterations = (L + NL > 100) ? base * 5 : base;       // consensus_utils.cpp:12-13
         CellResult r;
-        se2_wave_solve<M, NL, STAGED, W, se2_err_store<M>(), IPC_GROUP_KEEP_TRIAL>(P, lo, L, cand, iterations, sh, cst, wlo,
-                                                                                   wstride, r, box, seq, &seq);
+        se2_wave_solve<M, NL, STAGED, W, se2_err_store<M>(), IPC_GROUP_KEEP_TRIAL, IPC_GROUP_LAZY_SD>(P, lo, L, cand, iterations, sh, cst,
+                                                                                                      wlo, wstride, r, box, seq, &seq);
         if (wsub == 0 && lane == 0) {
             out.max_chi2[c] = r.max_chi2;
             out.chi2_total[c] = r.chi2_total;

@@ -245,7 +245,29 @@ __device__ __forceinline__ void unpark_pose(const ParkedPose& p, Pose2& Y)
     Y.c = __hiloint2double(h3, l3); Y.s = __hiloint2double(h4, l4);
 }
 
-template <int M, int NL, bool STAGED, int W = 1, int E_STORE = se2_err_store<M>(), bool KEEP_TRIAL = false>
+// LAZY_SD (the se2_*_kernel_lz kernels): b^T H b, alpha = b^T b / b^T H b and |h_sd| are read by a steepest-descent or
+// dog-leg trial only, and most iterations accept the Gauss-Newton step at their first trial.  Phases B1 and B2 then form
+// none of the three (no J b and quadratic form per slot, no information matrix loaded for it, no hand-off of b to the
+// next lane -- in the pair kernels one mailbox exchange --, no b at the loop end points, no division, no square root);
+// sd_terms() forms them, the same expressions reduced through the same network in the same order, at the first point of
+// the trial loop that reads them: at most once per iteration, in most iterations never.  Same bits (see sd_terms).
+//
+// The reduction network of entry 1 of wave_sum16_store (block_prims.hpp) alone: that entry is b^T H b in phase B1.  Row 0
+// of the packed value -- lanes l, l + 16, l + 32, l + 48 added as (l + (l + 32)) + ((l + 16) + (l + 48)), then the row
+// scan -- takes nothing from the three entries packed beside it, so they are zeros here; lane 15 holds the sum.
+__device__ __forceinline__ double wave_sum16_entry1(double v)
+{
+    const double r0 = pair32(v, 0.0);
+    double q = pair16(r0, 0.0);
+    q = row_inclusive_scan(q);
+    return read_lane(q, 15);
+}
+// b^T b beyond this (or not a number) makes a LAZY_SD iteration form the steepest-descent terms at its head, as the other
+// kernels do: see the trial loop.
+constexpr double kLazySdMaxBb = 0x1p500;
+
+template <int M, int NL, bool STAGED, int W = 1, int E_STORE = se2_err_store<M>(), bool KEEP_TRIAL = false,
+          bool LAZY_SD = false>
 __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int L, const int (&cand)[2], int iterations,
                                WaveScratch<NL>& sh, const double* cst, int wlo, int wstride, CellResult& res,
                                PairBox* box = nullptr, int seq0 = 0, int* seq_out = nullptr)
@@ -265,7 +287,7 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
     // ---- exchange among the W waves of the cell: every wave posts up to 8 doubles and waits for
     // all others; peer(o, k) then reads wave o's value k.  Also the cell's barrier. ----
 #ifdef IPC_PHASE_TIMING
-    unsigned long long gnEvals = 0, gnRejected = 0, nBig = 0, tmBig = 0, tmSmall = 0;
+    unsigned long long gnEvals = 0, gnRejected = 0, nBig = 0, tmBig = 0, tmSmall = 0, nSd = 0;
     unsigned long long tmA = 0, tmB1 = 0, tmB2 = 0, tmC = 0, tmT = 0, tmW = 0, tmK = 0, tm0 = __builtin_amdgcn_s_memtime();
 #define IPC_WTICK(acc) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); acc += t_ - tm0; tm0 = t_; }
 #else
@@ -429,6 +451,13 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
                 if (lf[l] == 0) { pf[0] = gauge.x; pf[1] = gauge.y; pf[2] = gauge.th; pf[3] = gauge.c; pf[4] = gauge.s; }
                 if (lt[l] == 0) { pt[0] = gauge.x; pt[1] = gauge.y; pt[2] = gauge.th; pt[3] = gauge.c; pt[4] = gauge.s; }
             }
+        if constexpr (LAZY_SD) {                     // b at a gauge end point is zero, and sd_terms stores the other end points only
+#pragma unroll
+            for (int l = 0; l < NL; ++l) {
+                if (lf[l] == 0) { sh.lvec[l][0][0] = 0.0; sh.lvec[l][0][1] = 0.0; sh.lvec[l][0][2] = 0.0; }
+                if (lt[l] == 0) { sh.lvec[l][1][0] = 0.0; sh.lvec[l][1][1] = 0.0; sh.lvec[l][1][2] = 0.0; }
+            }
+        }
     }
 
     // chain constants: local edge index of slot s is eloc + s (idle lanes are parked on edge 0;
@@ -751,6 +780,7 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
         launder();
         {
             // b at the loop end points (the gauge end point carries zero)
+            if constexpr (!LAZY_SD) {
 #pragma unroll
             for (int l = 0; l < NL; ++l) {
                 if (gl == 0) {
@@ -764,14 +794,16 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
                     if (st_[l] == s && gl == ot[l]) { sh.lvec[l][1][0] = bx[s]; sh.lvec[l][1][1] = by[s]; sh.lvec[l][1][2] = bth[s]; }
                 }
             }
+            }
             // group 1: b^T b, b^T H b, W_1 (3), M_11 (6); group 2: W_2 (3), M_22 (6), M_12 (6)
+            // (LAZY_SD: entry 1 stays zero here, sd_terms reduces b^T H b where a trial reads it)
             double v1[16], v2[16];
 #pragma unroll
             for (int k = 0; k < 16; ++k) { v1[k] = 0.0; v2[k] = 0.0; }
             v1[0] = bbp;
             double qbx, qby, qbth;
-            prev3(bx[M - 1], by[M - 1], bth[M - 1], qbx, qby, qbth);
-            constexpr int kWantB = 2 | 4 | 8 | kErrWantBC;
+            if constexpr (!LAZY_SD) prev3(bx[M - 1], by[M - 1], bth[M - 1], qbx, qby, qbth);
+            constexpr int kWantB = 2 | (LAZY_SD ? 0 : 4) | 8 | kErrWantBC;
             SlotConst Kn;
             if (PF) ld_slot(0, Kn, IntC<kWantB>{});
 #pragma unroll
@@ -782,10 +814,12 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
                 const Pose2& a = s == 0 ? a0 : X[s - 1];
                 const bool v = j0 + s <= L;
                 const double cz = K.cz, sz = K.sz;
+                if constexpr (!LAZY_SD) {
                 double wx, wy, wth;
                 se2_apply_J(a, X[s], cz, sz, qbx, qby, qbth, bx[s], by[s], bth[s], wx, wy, wth);
                 const double hq = K.om.quad(wx, wy, wth);
                 v1[1] += v ? hq : 0.0;
+                }
                 const Sym3 sg = K.sg;
                 const double c = a.c * cz - a.s * sz, sn = a.s * cz + a.c * sz;
                 const double kx = -(X[s].y - gauge.y), ky = X[s].x - gauge.x;
@@ -819,7 +853,11 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
 #pragma unroll
                     for (int k = 0; k < 6; ++k) { v2[3 + k] += m2 * psi[k]; v2[9 + k] += m12 * psi[k]; }
                 }
-                qbx = bx[s]; qby = by[s]; qbth = bth[s];
+                if constexpr (!LAZY_SD) { qbx = bx[s]; qby = by[s]; qbth = bth[s]; }
+                if constexpr (LAZY_SD)
+                    asm volatile("" : "+v"(v1[0]), "+v"(v1[2]), "+v"(v1[3]), "+v"(v1[4]), "+v"(v1[5]),
+                                 "+v"(v1[6]), "+v"(v1[7]), "+v"(v1[8]), "+v"(v1[9]), "+v"(v1[10]) : : "memory");
+                else
                 asm volatile("" : "+v"(v1[0]), "+v"(v1[1]), "+v"(v1[2]), "+v"(v1[3]), "+v"(v1[4]), "+v"(v1[5]),
                              "+v"(v1[6]), "+v"(v1[7]), "+v"(v1[8]), "+v"(v1[9]), "+v"(v1[10]) : : "memory");
                 if constexpr (NL == 2)
@@ -874,22 +912,28 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
                 for (int k = 0; k < 6; ++k) mred[o][k] = sh.red[o][mb + k];
 #pragma unroll
                 for (int k = 0; k < 3; ++k) wred[o][k] = sh.red[o][wb + k];
-                bred[o][0] = sh.red[o][0]; bred[o][1] = sh.red[o][1];
+                bred[o][0] = sh.red[o][0];
+                if constexpr (!LAZY_SD) bred[o][1] = sh.red[o][1];
             }
             const int lo_ = i < k3 ? i : k3, hi_ = i < k3 ? k3 : i;
             const double sgv = sh.lc[l1].sg[lo_ * 3 - lo_ * (lo_ - 1) / 2 + (hi_ - lo_)];
-            // operands of the loops' own b^T H b term (lanes >= NL read loop 0's and drop the result)
+            // operands of the loops' own b^T H b term (lanes >= NL read loop 0's and drop the result; LAZY_SD: sd_terms)
+            Pose2 qa, qb;
+            double qcz, qsz;
+            Sym3 qom;
+            double qv[2][3];
+            if constexpr (!LAZY_SD) {
             const LoopConst& qq = sh.lc[lq_l];
             const LoopState& sq = sh.ls[cur][lq_l];
-            const Pose2 qa{sq.pf[0], sq.pf[1], sq.pf[2], sq.pf[3], sq.pf[4]};
-            const Pose2 qb{sq.pt[0], sq.pt[1], sq.pt[2], sq.pt[3], sq.pt[4]};
-            const double qcz = qq.cz, qsz = qq.sz;
-            const Sym3 qom{qq.om[0], qq.om[1], qq.om[2], qq.om[3], qq.om[4], qq.om[5]};
-            double qv[2][3];
+            qa = Pose2{sq.pf[0], sq.pf[1], sq.pf[2], sq.pf[3], sq.pf[4]};
+            qb = Pose2{sq.pt[0], sq.pt[1], sq.pt[2], sq.pt[3], sq.pt[4]};
+            qcz = qq.cz; qsz = qq.sz;
+            qom = Sym3{qq.om[0], qq.om[1], qq.om[2], qq.om[3], qq.om[4], qq.om[5]};
 #pragma unroll
             for (int e = 0; e < 2; ++e)
 #pragma unroll
                 for (int k = 0; k < 3; ++k) qv[e][k] = sh.lvec[lq_l][e][k];
+            }
             __builtin_amdgcn_sched_barrier(0);
             // -- Gamma, and its entries to the lanes that use them: row i of loop l1 and row k3 of loop l2 for S[r][c],
             // six cross-lane reads, one wait (nu's column of Gamma is fetched with mu, behind the pivots) --
@@ -920,6 +964,12 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
                 for (int o = 1; o < W; ++o) w[k] += wred[o][k];
             }
             bb = bred[0][0];
+            if constexpr (LAZY_SD) {
+                bHb = 0.0;
+#pragma unroll
+                for (int o = 1; o < W; ++o) bb += bred[o][0];
+                IPC_PIN1(bb);
+            } else {
             bHb = bred[0][1];
 #pragma unroll
             for (int o = 1; o < W; ++o) { bb += bred[o][0]; bHb += bred[o][1]; }
@@ -931,6 +981,7 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
                 for (int l = 0; l < NL; ++l) bHb += read_lane(lq, l);
             }
             IPC_PIN2(bb, bHb);
+            }
             __builtin_amdgcn_sched_barrier(0);
             // -- assembly --
             double val;
@@ -960,12 +1011,14 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
                 inv = fma(fma(-piv, inv, 1.0), inv, inv);
                 inv = fma(fma(-piv, inv, 1.0), inv, inv);
                 // independent of the solve
+                if constexpr (!LAZY_SD) {
                 if (k == 0) {
                     alpha = bb / bHb;
                     IPC_PIN1(alpha);
                 } else if (k == 1) {
                     hsdNorm = sqrt(alpha * alpha * bb);
                     IPC_PIN1(hsdNorm);
+                }
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 val = (r == k) ? rowk * inv : fma(-(colk * rowk), inv, val);
@@ -1066,6 +1119,118 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
         // step at its first trial) and one more such step cannot move any edge's chi2 by more than
         // 2 sqrt(term_eps) relative; g2o would still run its trial loop to Terminate
         if (lastGN && hgnNorm < delta && fabs(bh) < term_scale * currentChi) { it_done = it + 1; tries_total += maxTrials; flags |= 1; break; }
+        // ---- steepest-descent terms of a LAZY_SD kernel: b^T H b, alpha, |h_sd|, what phases B1 and B2 left out ----
+        // The same bits as there: the per-slot term is the same two helpers on the same operands (the committed poses and
+        // b have not moved: no trial has been accepted yet); a lane adds its slots from 0.0 in slot order with the same
+        // select; the wave's sum goes through entry 1's place in wave_sum16_store's network; the waves' sums are added in
+        // wave order and the loops' own terms after them in loop order; alpha and |h_sd| are the same expressions.
+        // Pairs: both waves enter together -- the caller branches on the cell sums, delta and the trial count, which both
+        // waves hold bit-identically -- and run the same two exchanges, so their sequence numbers stay in step.  The first
+        // exchange carries what prev0 and prev3 carry apart elsewhere (the first wave's last pose and last b: 8 values).
+        // sh.lvec is written and read nowhere else in these kernels and sh.red not at all here (the wave's sum crosses
+        // in the mailbox).  A wave's lvec stores precede its post of the first exchange and both waves read lvec behind
+        // the second; the next sd_terms (a later iteration) stores again only behind the exchanges of at least one trial
+        // sweep, which a wave passes only after its partner has posted them, that is after the partner's reads above in
+        // its program order (LDS operations of one wave complete in order).  The partner's B2 reads of sh.red and of the
+        // loop state lie before its phase C exchanges, which this wave has passed.
+        [[maybe_unused]] bool sdReady = false;
+        [[maybe_unused]] auto sd_terms = [&]() {
+#ifdef IPC_PHASE_TIMING
+            ++nSd;
+#endif
+            // (two comments in the assembly, each behind a scheduling barrier: tools/isa_loop_mix.py counts the block apart)
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile(";ipc_sd_terms_begin" : : : "memory");
+            opaque();
+            launder();
+            // b at the loop end points (the gauge end point carries zero: stored once, with the gauge's pose, before the loop)
+#pragma unroll
+            for (int l = 0; l < NL; ++l) {
+#pragma unroll
+                for (int s = 0; s < M; ++s) {
+                    if (!((ownSlots >> s) & 1u)) continue;
+                    if (sf[l] == s && gl == of[l]) { sh.lvec[l][0][0] = bx[s]; sh.lvec[l][0][1] = by[s]; sh.lvec[l][0][2] = bth[s]; }
+                    if (st_[l] == s && gl == ot[l]) { sh.lvec[l][1][0] = bx[s]; sh.lvec[l][1][1] = by[s]; sh.lvec[l][1][2] = bth[s]; }
+                }
+            }
+            // pose j-1 and b of the lane below
+            Pose2 cr = gauge;
+            double c0 = 0.0, c1 = 0.0, c2 = 0.0;
+            if constexpr (W > 1) {
+                double a[8] = {read_lane(X[M - 1].x, 63), read_lane(X[M - 1].y, 63), read_lane(X[M - 1].th, 63),
+                               read_lane(X[M - 1].c, 63), read_lane(X[M - 1].s, 63),
+                               read_lane(bx[M - 1], 63), read_lane(by[M - 1], 63), read_lane(bth[M - 1], 63)};
+                post_wait(a, 8);
+                if (wsub > 0) {
+                    cr.x = peer(wsub - 1, 0); cr.y = peer(wsub - 1, 1); cr.th = peer(wsub - 1, 2); cr.c = peer(wsub - 1, 3);
+                    cr.s = peer(wsub - 1, 4);
+                    c0 = peer(wsub - 1, 5); c1 = peer(wsub - 1, 6); c2 = peer(wsub - 1, 7);
+                }
+            } else {
+                wave_sync();                          // sh.lvec visible
+            }
+            Pose2 as0;
+            as0.x = lane_prev(X[M - 1].x, cr.x); as0.y = lane_prev(X[M - 1].y, cr.y); as0.th = lane_prev(X[M - 1].th, cr.th);
+            as0.c = lane_prev(X[M - 1].c, cr.c); as0.s = lane_prev(X[M - 1].s, cr.s);
+            double qbx = lane_prev(bx[M - 1], c0), qby = lane_prev(by[M - 1], c1), qbth = lane_prev(bth[M - 1], c2);
+            double acc = 0.0;
+            constexpr int kWantS = 2 | 4;
+            SlotConst Kn;
+            if (PF) ld_slot(0, Kn, IntC<kWantS>{});
+#pragma unroll
+            for (int s = 0; s < M; ++s) {
+                SlotConst K;
+                if (PF) { K = Kn; if (s + 1 < M) ld_slot(s + 1, Kn, IntC<kWantS>{}); }
+                else ld_slot(s, K, IntC<kWantS>{});
+                const Pose2& a = s == 0 ? as0 : X[s - 1];
+                const bool v = j0 + s <= L;
+                const double cz = K.cz, sz = K.sz;
+                double wx, wy, wth;
+                se2_apply_J(a, X[s], cz, sz, qbx, qby, qbth, bx[s], by[s], bth[s], wx, wy, wth);
+                const double hq = K.om.quad(wx, wy, wth);
+                acc += v ? hq : 0.0;
+                qbx = bx[s]; qby = by[s]; qbth = bth[s];
+                IPC_PIN1(acc);
+                IPC_SLOT_FENCE();
+            }
+            const double t = wave_sum16_entry1(acc);
+            if constexpr (W > 1) {
+                double a[8] = {t, 0, 0, 0, 0, 0, 0, 0};
+                post_wait(a, 1);
+                bHb = wsub == 0 ? t : peer(0, 0);
+#pragma unroll
+                for (int o = 1; o < W; ++o) bHb += o == wsub ? t : peer(o, 0);
+            } else {
+                bHb = t;
+            }
+            {
+                // the loops' own term (lanes >= NL read loop 0's operands and drop the result)
+                int bl = lane;
+                asm volatile("" : "+v"(bl));
+                const int lq_l = bl < NL ? bl : 0;
+                const LoopConst& qq = sh.lc[lq_l];
+                const LoopState& sq = sh.ls[cur][lq_l];
+                const Pose2 qa{sq.pf[0], sq.pf[1], sq.pf[2], sq.pf[3], sq.pf[4]};
+                const Pose2 qb{sq.pt[0], sq.pt[1], sq.pt[2], sq.pt[3], sq.pt[4]};
+                const double qcz = qq.cz, qsz = qq.sz;
+                const Sym3 qom{qq.om[0], qq.om[1], qq.om[2], qq.om[3], qq.om[4], qq.om[5]};
+                double qv[2][3];
+#pragma unroll
+                for (int e = 0; e < 2; ++e)
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) qv[e][k] = sh.lvec[lq_l][e][k];
+                double wx, wy, wth;                        // (loop_quad)
+                se2_apply_J(qa, qb, qcz, qsz, qv[0][0], qv[0][1], qv[0][2], qv[1][0], qv[1][1], qv[1][2], wx, wy, wth);
+                const double lq = bl < NL ? qom.quad(wx, wy, wth) : 0.0;
+#pragma unroll
+                for (int l = 0; l < NL; ++l) bHb += read_lane(lq, l);
+            }
+            alpha = bb / bHb;
+            hsdNorm = sqrt(alpha * alpha * bb);
+            IPC_PIN3(bHb, alpha, hsdNorm);
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile(";ipc_sd_terms_end" : : : "memory");
+        };
         // ---- trial loop ----
         const double deltaAtEntry = delta;
         bool goodStep = false, dlReady = false;
@@ -1073,6 +1238,27 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
         int numTries = 0;
         do {
             ++numTries;
+            if constexpr (LAZY_SD) {
+                // The first point of this iteration that reads b^T H b, alpha or |h_sd|: a trial that is not Gauss-Newton,
+                // the first one or the one after a rejected Gauss-Newton trial (whose retry loop has taken delta down to
+                // |h_gn| or below; once a trial is not Gauss-Newton none of this iteration is again).  A Gauss-Newton trial
+                // reads b^T H b in one place, h_dl^T H h_dl = p p bHb + 2 p q bb + q q hHh with p = 0.0 and q = 1.0, and
+                // evaluates it with bHb = 0.0 here.  The bits are those of the finite b^T H b: p p bHb is then +0 or -0;
+                // 2 p q bb is +0 exactly, since bb, a sum of squares, is not negative; (+-0) + (+0) is +0 under round to
+                // nearest, also where the two are contracted into one fused multiply-add (the exact product +-0 plus +0);
+                // so what is added to q q hHh is +0 in both kernels, whatever the sign of b^T H b.  b h_dl = p bb + q bh
+                // does not hold b^T H b.  Only a b^T H b that is infinite or not a number differs: 0 times it poisons the
+                // gain and the other kernels then stop the cell.  So where bb is not a number or beyond 2^500 the terms
+                // are formed before the first trial whatever its type, as the other kernels do.  Below the bound every
+                // component of b is below 2^250 in magnitude, a slot's J b is at most (2 + 2 |r|) times two of them (r the
+                // edge's relative translation, the rotations are unit), and its quadratic form at most nine times the
+                // largest information entry times that squared, and a sum of finite terms of this size stays finite.  That
+                // is finite UNDER AN ASSUMPTION ON THE DATA, which nothing here enforces: information entries and distances
+                // between neighbouring poses below 2^160.  Data beyond it would give the other kernels a gain that is not a
+                // number where this one's is finite.
+                // (every lane holds the same values; the ballot says so, which makes this a scalar branch)
+                if (!sdReady && __ballot(!(hgnNorm < delta) || !(bb <= kLazySdMaxBb)) != 0ull) { sd_terms(); sdReady = true; }
+            }
             int stepType;                             // 0 GN, 1 SD, 2 DL
             double beta = 0.0, sdScale = 0.0;
             if (hgnNorm < delta) stepType = 0;
@@ -1178,6 +1364,7 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
         atomicAdd(d + 6, (unsigned long long)it_done); atomicAdd(d + 7, (unsigned long long)evals);
         atomicAdd(d + 8, (unsigned long long)it_done * (unsigned long long)L);
         atomicAdd(d + 9, 1ull); atomicAdd(d + 10, tmK); atomicAdd(d + 11, (unsigned long long)(evals - 1 - it_done)); atomicAdd(d + 12, gnEvals); atomicAdd(d + 13, gnRejected); atomicAdd(d + 14, nBig); atomicAdd(d + 15, tmBig); atomicAdd(d + 1024, tmSmall);
+        if constexpr (LAZY_SD) atomicAdd(d + 1025, nSd);      // iterations that ran sd_terms
     }
 #endif
 

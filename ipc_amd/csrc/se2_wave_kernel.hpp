@@ -1,9 +1,11 @@
 // Wave kernels of the SE(2) cell solver (se2_wave_cell.hpp): persistent workgroups of four
 // independent waves, each solving one cell at a time from a shared work queue.
 //
-// Two kernel templates, one text (se2_wave_kernel_def.hpp): se2_wave_kernel re-sweeps an accepted trial to commit it;
-// se2_wave_kernel_kt (kept trial) reads it back from the accumulator registers where the trial sweep parked it.
-// se2_wave.hip instantiates the first, se2_wave_kt.hip the second.
+// Three kernel templates, one text (se2_wave_kernel_def.hpp): se2_wave_kernel re-sweeps an accepted trial to commit it;
+// se2_wave_kernel_kt (kept trial) reads it back from the accumulator registers where the trial sweep parked it;
+// se2_wave_kernel_lz (LAZY_SD of se2_wave_solve) forms the steepest-descent terms only where a trial reads them and
+// commits as the default policy's kernel of that M does (kept trial up to M = 9, re-sweep beyond).
+// se2_wave.hip instantiates the first, se2_wave_kt.hip the second, se2_wave_lz.hip the third.
 #pragma once
 #include "cell_kernels.hpp"
 #include "se2_wave_cell.hpp"
@@ -21,6 +23,7 @@ constexpr int se2_waves() { return M <= IPC_SE2_DENSE_MAXM ? 8 : 4; }
 
 #define IPC_WAVE_KERNEL_NAME se2_wave_kernel
 #define IPC_WAVE_KEEP_TRIAL false
+#define IPC_WAVE_LAZY_SD false
 #include "se2_wave_kernel_def.hpp"
 #undef IPC_WAVE_KERNEL_NAME
 #undef IPC_WAVE_KEEP_TRIAL
@@ -29,12 +32,21 @@ constexpr int se2_waves() { return M <= IPC_SE2_DENSE_MAXM ? 8 : 4; }
 #include "se2_wave_kernel_def.hpp"
 #undef IPC_WAVE_KERNEL_NAME
 #undef IPC_WAVE_KEEP_TRIAL
+#undef IPC_WAVE_LAZY_SD
+#define IPC_WAVE_KERNEL_NAME se2_wave_kernel_lz
+#define IPC_WAVE_KEEP_TRIAL (M <= kLazyKeepTrialMaxM)
+#define IPC_WAVE_LAZY_SD true
+#include "se2_wave_kernel_def.hpp"
+#undef IPC_WAVE_KERNEL_NAME
+#undef IPC_WAVE_KEEP_TRIAL
+#undef IPC_WAVE_LAZY_SD
 
 // (only the chosen template is instantiated: a translation unit emits the kernels it launches and no others)
-template <int M, int NL, bool STAGED, bool KEEP_TRIAL>
+template <int M, int NL, bool STAGED, bool KEEP_TRIAL, bool LAZY_SD>
 constexpr auto se2_wave_kernel_of()
 {
-    if constexpr (KEEP_TRIAL) return &se2_wave_kernel_kt<M, NL, STAGED>;
+    if constexpr (LAZY_SD) return &se2_wave_kernel_lz<M, NL, STAGED>;
+    else if constexpr (KEEP_TRIAL) return &se2_wave_kernel_kt<M, NL, STAGED>;
     else return &se2_wave_kernel<M, NL, STAGED>;
 }
 
@@ -43,7 +55,7 @@ constexpr auto se2_wave_kernel_of()
 #endif
 constexpr int kLdsBudget = IPC_LDS_BUDGET;
 
-template <int M, int NL, bool KEEP_TRIAL>
+template <int M, int NL, bool KEEP_TRIAL, bool LAZY_SD = false>
 static hipError_t launch_wave_one(int n, hipStream_t st, const Se2View& P, const int2* cells, SolveParams prm, CellOut out,
                                   unsigned* counter, int n_cu)
 {
@@ -54,12 +66,12 @@ static hipError_t launch_wave_one(int n, hipStream_t st, const Se2View& P, const
     const size_t staged = scratch + sizeof(double) * (size_t)F_SG * wstride;
     const int groups = std::max(1, std::min(n_cu, (n + kWavesPerGroup - 1) / kWavesPerGroup));
     if (staged <= (size_t)kLdsBudget) {
-        auto k = se2_wave_kernel_of<M, NL, true, KEEP_TRIAL>();
+        auto k = se2_wave_kernel_of<M, NL, true, KEEP_TRIAL, LAZY_SD>();
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)staged);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k, dim3(groups), dim3(64 * kWavesPerGroup), staged, st, P, cells, n, counter, prm, out, 0, E, wstride);
     } else {
-        auto k = se2_wave_kernel_of<M, NL, false, KEEP_TRIAL>();
+        auto k = se2_wave_kernel_of<M, NL, false, KEEP_TRIAL, LAZY_SD>();
         hipLaunchKernelGGL(k, dim3(groups), dim3(64 * kWavesPerGroup), scratch, st, P, cells, n, counter, prm, out, 0, E, wstride);
     }
     return hipGetLastError();

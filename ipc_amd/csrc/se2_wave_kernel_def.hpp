@@ -3,7 +3,8 @@
 //   IPC_WAVE_KERNEL_NAME   name of the __global__ template
 //   IPC_WAVE_KEEP_TRIAL    KEEP_TRIAL of se2_wave_solve: false, an accepted trial is re-swept to commit; true, it is
 //                          read back from the accumulator registers where the trial sweep parked it
-// (no include guard; one text for both kernels and no function between the kernel and se2_wave_solve, for the reason
+//   IPC_WAVE_LAZY_SD       LAZY_SD of se2_wave_solve: true, the steepest-descent terms are formed only where a trial reads them
+// (no include guard; one text for all kernels and no function between the kernel and se2_wave_solve, for the reason
 // given in se2_group_kernel_def.hpp).
 template <int M, int NL, bool STAGED>
 __global__ __launch_bounds__((64 * se2_waves<M>()), 1) void IPC_WAVE_KERNEL_NAME(Se2View P, const int2* cells, int ncells,
@@ -39,8 +40,8 @@ __global__ __launch_bounds__((64 * se2_waves<M>()), 1) void IPC_WAVE_KERNEL_NAME
         const int base = NL == 1 ? prm.fast_iter : prm.slow_iter;
         const int iterations = (L + NL > 100) ? base * 5 : base;       // consensus_utils.cpp:12-13
         CellResult r;
-        se2_wave_solve<M, NL, STAGED, 1, se2_err_store<M>(), IPC_WAVE_KEEP_TRIAL>(P, lo, L, cand, iterations, sh, cst, wlo,
-                                                                                  wstride, r);
+        se2_wave_solve<M, NL, STAGED, 1, se2_err_store<M>(), IPC_WAVE_KEEP_TRIAL, IPC_WAVE_LAZY_SD>(P, lo, L, cand, iterations, sh, cst,
+                                                                                                    wlo, wstride, r);
         if (lane == 0) {
             out.max_chi2[c] = r.max_chi2;
             out.chi2_total[c] = r.chi2_total;

@@ -31,6 +31,7 @@ VALU_CLASSES = ("f64", "f64_cmp", "f64_cvt", "accvgpr", "v_mov", "v_int", "cndma
 ALL_CLASSES = VALU_CLASSES + ("salu", "s_nop", "s_waitcnt", "lds", "scratch", "vmem", "smem")
 _F64_ROUND = ("v_rndne_f64", "v_floor_f64", "v_ceil_f64", "v_trunc_f64", "v_fract_f64")
 _INSN = re.compile(r"^\s+([a-z][a-z0-9_]+)(?:\s|$)")
+SD_BEGIN, SD_END = ";ipc_sd_terms_begin", ";ipc_sd_terms_end"     # marker comments of se2_wave_solve's sd_terms()
 
 
 def classify(line):
@@ -87,7 +88,15 @@ def _demangle(names):
 
 def short_name(demangled):
     """se2_wave_kernel<9, 2, true> -> w9/nl2/staged; se2_group_kernel<2, 9, 2, true> -> p9/nl2/staged (W = 4: q);
-    the kept-trial kernels se2_wave_kernel_kt / se2_group_kernel_kt -> kw9/..., kp9/..."""
+    the kept-trial kernels se2_wave_kernel_kt / se2_group_kernel_kt -> kw9/..., kp9/...; the lazy steepest-descent
+    kernels se2_wave_kernel_lz / se2_group_kernel_lz -> lw9/..., lp9/..."""
+    m = re.search(r"se2_wave_kernel_lz<(\d+), (\d+), (true|false)>", demangled)
+    if m:
+        return "lw%s/nl%s/%s" % (m.group(1), m.group(2), "staged" if m.group(3) == "true" else "unstaged")
+    m = re.search(r"se2_group_kernel_lz<(\d+), (\d+), (\d+), (true|false)>", demangled)
+    if m:
+        return "l%s%s/nl%s/%s" % ({"2": "p", "4": "q"}.get(m.group(1), "g" + m.group(1)), m.group(2), m.group(3),
+                                  "staged" if m.group(4) == "true" else "unstaged")
     m = re.search(r"se2_wave_kernel_kt<(\d+), (\d+), (true|false)>", demangled)
     if m:
         return "kw%s/nl%s/%s" % (m.group(1), m.group(2), "staged" if m.group(3) == "true" else "unstaged")
@@ -197,11 +206,21 @@ def analyse(path, match=None):
         c, ops = count(body[loop[0]:loop[1] + 1])
         valu = sum(c[k] for k in VALU_CLASSES)
         md = meta[name]
+        # the sd_terms() block of a lazy steepest-descent kernel, between its two marker comments (once each, in order,
+        # inside the loop: else the block counts as not delimited)
+        seg = body[loop[0]:loop[1] + 1]
+        mb = [i for i, l in enumerate(seg) if SD_BEGIN in l]
+        me = [i for i, l in enumerate(seg) if SD_END in l]
+        sd_valu = None
+        if len(mb) == 1 and len(me) == 1 and mb[0] < me[0]:
+            sc, _ = count(seg[mb[0]:me[0]])
+            sd_valu = sum(sc[k] for k in VALU_CLASSES)
         rows.append({
             "kernel": short_name(d), "loop_lines": loop[1] - loop[0] + 1,
             "counts": {k: c[k] for k in ALL_CLASSES}, "valu": valu,
             "f64_all": c["f64"] + c["f64_cmp"] + c["f64_cvt"],
             "f64_share": (c["f64"] + c["f64_cmp"] + c["f64_cvt"]) / valu if valu else 0.0,
+            "sd_block_valu": sd_valu,
             "copy_lane": c["accvgpr"] + c["lane"],
             "execz": ops["s_cbranch_execz"] + ops["s_cbranch_execnz"],
             "saveexec": sum(v for k, v in ops.items() if "saveexec" in k),
@@ -226,6 +245,8 @@ def render(rows, out=sys.stdout):
                 out.write("    %-10s %6d  %.3f of VALU\n" % (k, c[k], c[k] / r["valu"]))
         out.write("    %-10s %6d  %.3f of VALU   (f64 + f64_cmp + f64_cvt: every v_*_f64)\n" % ("FP64 all", r["f64_all"], r["f64_share"]))
         out.write("    %-10s %6d\n" % ("all VALU", r["valu"]))
+        if r.get("sd_block_valu") is not None:
+            out.write("    %-10s %6d   (VALU of the sd_terms block, between its markers)\n" % ("sd_terms", r["sd_block_valu"]))
         for k in ALL_CLASSES[len(VALU_CLASSES):]:
             if c[k]:
                 out.write("    %-10s %6d\n" % (k, c[k]))
@@ -243,7 +264,8 @@ def parse_report(path):
         if not m:
             continue
         g = lambda pat: int(re.search(pat, blk).group(1))
-        out[m.group(1)] = {"f64_all": g(r"FP64 all\s+(\d+)"), "valu": g(r"all VALU\s+(\d+)"),
+        sd = re.search(r"^    sd_terms\s+(\d+)", blk, re.M)
+        out[m.group(1)] = {"sd_block_valu": int(sd.group(1)) if sd else None, "f64_all": g(r"FP64 all\s+(\d+)"), "valu": g(r"all VALU\s+(\d+)"),
                            "copy_lane": g(r"accvgpr\+lane (\d+)"), "sgpr_spill_count": g(r"sgpr_spill (\d+)"),
                            "vgpr_spill_count": g(r"vgpr_spill (\d+)"), "scratch_bytes": g(r"scratch (\d+) B")}
     return out
@@ -252,7 +274,9 @@ def parse_report(path):
 # ---- the recipe: assembly of the hot instantiations, one per compile (shipped flags, device side only) ----
 def hot_units():
     """{tag: (translation unit, [-D...])}: w9 w11 w13 of se2_wave.hip, p7 p9 p11 of se2_pair.hip, and the kept-trial
-    kernels kw5 .. kw11 of se2_wave_kt.hip and kp7 kp9 kp11 of se2_pair_kt.hip (with w5 and w7, their counterparts)."""
+    kernels kw5 .. kw11 of se2_wave_kt.hip and kp7 kp9 kp11 of se2_pair_kt.hip (with w5 and w7, their counterparts); the
+    lazy steepest-descent kernels lw5 .. lw13 of se2_wave_lz.hip and lp7 lp9 lp11 of se2_pair_lz.hip (counterparts: what the
+    default policy names for that M, kw5 kw7 kw9 w11 w13 and kp7 kp9 p11)."""
     u = {}
     for m in (9, 11, 13):
         u["w%d" % m] = ("se2_wave.hip", ["-DIPC_WAVE_ONLY_M=%d" % m])
@@ -264,6 +288,10 @@ def hot_units():
         u["kw%d" % m] = ("se2_wave_kt.hip", ["-DIPC_WAVE_KT_ONLY_M=%d" % m])
     for m in (7, 9, 11):
         u["kp%d" % m] = ("se2_pair_kt.hip", ["-DIPC_PAIR_KT_ONLY_M=%d" % m])
+    for m in (5, 7, 9, 11, 13):
+        u["lw%d" % m] = ("se2_wave_lz.hip", ["-DIPC_WAVE_LZ_ONLY_M=%d" % m])
+    for m in (7, 9, 11):
+        u["lp%d" % m] = ("se2_pair_lz.hip", ["-DIPC_PAIR_LZ_ONLY_M=%d" % m])
     return u
 
 
