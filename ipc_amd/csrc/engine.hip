@@ -621,12 +621,13 @@ static const char* kDefaultPolicy = "w1,w3,kw5,kw7,kw9,w11,w13,kp7,kp9,p11,q7,q9
 // partner inside one library; =2 substitutes every M that has a lazy kernel, listed below or not (the bitwise test and
 // the per-bin gate runs reach the unlisted ones that way).  Only the M listed here are substituted by default: the
 // kernels that passed the static gate (tests/test_se2_lazy_sd_loop_mix.py) and the measured one
-// (profiles/se2_lazy_sd_c2_kernel_gate.txt).
-// Every one of the eight is faster in its bin on the MI355X (-2.4 to -10.9 %); lw9, lp7 and lp9 are held back by the static
-// gate alone (two spilled vector registers, or two spilled scalar registers, more than the counterpart in one or two of
-// their four instantiations) and lw13 by its scratch: DESIGN.md 8 has the figures.
-static const int kLazySdWaveM[] = {5, 7, 11};            // for kw5, kw7, w11     (not 9: kw9, not 13: w13)
-static const int kLazySdPairM[] = {11};                  // for p11               (not 7, 9: kp7, kp9)
+// (profiles/se2_lazy_sd_c2_kernel_gate.txt, profiles/se2_lazy_gauge_c2_kernel_gate.txt).
+// Every one of the eight is faster in its bin on the MI355X; lw9 and lp9 are listed since they park the gauge pose in
+// accumulator registers by hand (PARK_GAUGE, se2_wave_cell.hpp: no spilled vector register in any instantiation) and lp7
+// since its "terms formed" flag is a bit of the flags word (SD_BIT: no more spilled scalar registers than kp7); lw13 is
+// held back by its scratch: DESIGN.md 8 has the figures.
+static const int kLazySdWaveM[] = {5, 7, 9, 11};         // for kw5, kw7, kw9, w11 (not 13: w13)
+static const int kLazySdPairM[] = {7, 9, 11};            // for kp7, kp9, p11
 static bool lazy_sd_serves(int variant, bool every)    // every: any M that has a lazy kernel (IPC_SE2_LAZY_SD=2, tests and gate runs)
 {
     bool wave = false, pair = false;

@@ -245,6 +245,26 @@ __device__ __forceinline__ void unpark_pose(const ParkedPose& p, Pose2& Y)
     Y.c = __hiloint2double(h3, l3); Y.s = __hiloint2double(h4, l4);
 }
 
+// PARK_GAUGE (the lazy kernels at M = 9): the gauge pose -- the cell's pose 0, the same in every lane, written once per cell
+// and read in every phase of every iteration -- lives in ten accumulator registers, by hand.  These kernels fill the vector
+// registers to the last one; left to the register allocator, one of the gauge's doubles (x or y) goes to the accumulator
+// file anyway and a second one no longer fits, which spills (lw9, lp9 un-staged: two spilled vector registers where kw9 and
+// kp9 have none).  Parked explicitly, every use reads the doubles it needs back at that point -- x, y in phases B1, B2 and C,
+// the whole pose where lane 0 takes it for its predecessor -- and no vector register holds any of it across the loop.
+// Copies only: same bits.
+struct ParkedD { int w[2]; };                        // one double as two accumulator registers
+__device__ __forceinline__ void park_d(ParkedD& p, double v)
+{
+    asm volatile("v_accvgpr_write_b32 %0, %2\n\tv_accvgpr_write_b32 %1, %3"
+                 : "=a"(p.w[0]), "=a"(p.w[1]) : "v"(__double2loint(v)), "v"(__double2hiint(v)));
+}
+__device__ __forceinline__ double unpark_d(const ParkedD& p)
+{
+    int l, h;
+    asm volatile("v_accvgpr_read_b32 %0, %2\n\tv_accvgpr_read_b32 %1, %3" : "=v"(l), "=v"(h) : "a"(p.w[0]), "a"(p.w[1]));
+    return __hiloint2double(h, l);
+}
+
 // LAZY_SD (the se2_*_kernel_lz kernels): b^T H b, alpha = b^T b / b^T H b and |h_sd| are read by a steepest-descent or
 // dog-leg trial only, and most iterations accept the Gauss-Newton step at their first trial.  Phases B1 and B2 then form
 // none of the three (no J b and quadratic form per slot, no information matrix loaded for it, no hand-off of b to the
@@ -274,6 +294,12 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
 {
     static_assert(W == 1 || W == 2 || W == 4, "one, two or four cooperating waves per cell");
     constexpr bool KEEP_E = E_STORE == 1, PARK_E = E_STORE == 2;
+    constexpr bool PARK_GAUGE = LAZY_SD && M == 9;
+    // lp7 alone: "sd_terms ran in this iteration" is a bit of `flags`, not a wave-uniform bool of its own carried across the
+    // trial loop (that one scalar state more cost lp7/nl1/staged two spilled scalar registers more than kp7 has); the bit
+    // never leaves the function
+    constexpr bool SD_BIT = LAZY_SD && M == 7 && W == 2;
+    constexpr int kSdFormedBit = 0x100;
     constexpr int NS = NL * 3;
     const double term_scale = P.term_eps / (double)(L + NL);   // 0: the test is off
     bool lastGN = false;
@@ -460,6 +486,21 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
         }
     }
 
+    // PARK_GAUGE: x, y, theta, cos, sin parked here, once per cell; `gauge` itself is not read below this point
+    [[maybe_unused]] ParkedD pg[PARK_GAUGE ? 5 : 1];
+    if constexpr (PARK_GAUGE) {
+        park_d(pg[0], gauge.x); park_d(pg[1], gauge.y); park_d(pg[2], gauge.th); park_d(pg[3], gauge.c); park_d(pg[4], gauge.s);
+    }
+    auto gauge_x = [&]() -> double { if constexpr (PARK_GAUGE) return unpark_d(pg[0]); else return gauge.x; };
+    auto gauge_y = [&]() -> double { if constexpr (PARK_GAUGE) return unpark_d(pg[1]); else return gauge.y; };
+    auto gauge_pose = [&]() -> Pose2 {
+        if constexpr (PARK_GAUGE) {
+            Pose2 g;
+            g.x = unpark_d(pg[0]); g.y = unpark_d(pg[1]); g.th = unpark_d(pg[2]); g.c = unpark_d(pg[3]); g.s = unpark_d(pg[4]);
+            return g;
+        } else return gauge;
+    };
+
     // chain constants: local edge index of slot s is eloc + s (idle lanes are parked on edge 0;
     // the partially filled lane reads up to M-1 records past the chain, which the window padding
     // and the record-array padding cover)
@@ -514,7 +555,7 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
     // pose j-1 of slot 0: slot M-1 of the lane below (lane 0 of the cell: the gauge; lane 0 of the
     // pair's second wave: lane 63 of the first, through the mailbox)
     auto prev0 = [&](const Pose2& last) -> Pose2 {
-        Pose2 cr = gauge;
+        Pose2 cr = gauge_pose();
         if constexpr (W > 1) {
             double a[8] = {read_lane(last.x, 63), read_lane(last.y, 63), read_lane(last.th, 63), read_lane(last.c, 63),
                            read_lane(last.s, 63), 0, 0, 0};
@@ -822,7 +863,7 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
                 }
                 const Sym3 sg = K.sg;
                 const double c = a.c * cz - a.s * sz, sn = a.s * cz + a.c * sz;
-                const double kx = -(X[s].y - gauge.y), ky = X[s].x - gauge.x;
+                const double kx = -(X[s].y - gauge_y()), ky = X[s].x - gauge_x();
                 const double cc = c * c, ss = sn * sn, cs = c * sn;
                 const double C00 = cc * sg.a00 - 2 * cs * sg.a01 + ss * sg.a11;
                 const double C01 = cs * (sg.a00 - sg.a11) + (cc - ss) * sg.a01;
@@ -940,7 +981,7 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
             double g1[3], g2[3], gam;
             {
                 const double Aq = gpc * gcz - gps * gsz, Bq = gps * gcz + gpc * gsz;
-                const double Kx = -(gty - gauge.y), Ky = gtx - gauge.x;
+                const double Kx = -(gty - gauge_y()), Ky = gtx - gauge_x();
                 gam = se2_gamma(Aq, Bq, Kx, Ky, gsig, g_i, g_a);
 #pragma unroll
                 for (int a = 0; a < 3; ++a) {
@@ -1068,7 +1109,7 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
                 }
                 const double cz = K.cz, sz = K.sz;
                 const double c = a.c * cz - a.s * sz, sn = a.s * cz + a.c * sz;
-                const double kx = -(X[s].y - gauge.y), ky = X[s].x - gauge.x;
+                const double kx = -(X[s].y - gauge_y()), ky = X[s].x - gauge_x();
                 const double wx = c * n0 + sn * n1, wy = -sn * n0 + c * n1, wth = -(kx * n0 + ky * n1) + n2;
                 double vx, vy, vth;
                 K.sg.mul(wx, wy, wth, vx, vy, vth);
@@ -1134,6 +1175,7 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
         // its program order (LDS operations of one wave complete in order).  The partner's B2 reads of sh.red and of the
         // loop state lie before its phase C exchanges, which this wave has passed.
         [[maybe_unused]] bool sdReady = false;
+        if constexpr (SD_BIT) flags &= ~kSdFormedBit;
         [[maybe_unused]] auto sd_terms = [&]() {
 #ifdef IPC_PHASE_TIMING
             ++nSd;
@@ -1154,7 +1196,7 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
                 }
             }
             // pose j-1 and b of the lane below
-            Pose2 cr = gauge;
+            Pose2 cr = gauge_pose();
             double c0 = 0.0, c1 = 0.0, c2 = 0.0;
             if constexpr (W > 1) {
                 double a[8] = {read_lane(X[M - 1].x, 63), read_lane(X[M - 1].y, 63), read_lane(X[M - 1].th, 63),
@@ -1257,6 +1299,9 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
                 // between neighbouring poses below 2^160.  Data beyond it would give the other kernels a gain that is not a
                 // number where this one's is finite.
                 // (every lane holds the same values; the ballot says so, which makes this a scalar branch)
+                if constexpr (SD_BIT) {
+                    if (!(flags & kSdFormedBit) && __ballot(!(hgnNorm < delta) || !(bb <= kLazySdMaxBb)) != 0ull) { sd_terms(); flags |= kSdFormedBit; }
+                } else
                 if (!sdReady && __ballot(!(hgnNorm < delta) || !(bb <= kLazySdMaxBb)) != 0ull) { sd_terms(); sdReady = true; }
             }
             int stepType;                             // 0 GN, 1 SD, 2 DL
@@ -1412,7 +1457,7 @@ __device__ __forceinline__ void se2_wave_solve(const Se2View& P, int lo_abs, int
     res.chi2_total = currentChi;
     res.iterations = it_done;
     res.tries = tries_total;
-    res.flags = flags;
+    res.flags = SD_BIT ? flags & ~kSdFormedBit : flags;
     res.evals = evals;
     if (seq_out) *seq_out = seq;
 }
