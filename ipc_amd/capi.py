@@ -44,6 +44,8 @@ SYMBOLS = [
 SYMBOLS_ONLINE_EXACT = ["ipc_set_max_exact_resume", "ipc_run_online_exact", "ipc_online_exact_state"]
 # the symbol include/ipc_amd_lazy_sd.h declares
 SYMBOLS_LAZY_SD = ["ipc_se2_lazy_sd_launches"]
+# every symbol include/ipc_amd_batch_exact.h declares (checked by tests/test_batch_exact_cpu.py)
+SYMBOLS_BATCH_EXACT = ["ipc_set_max_batch_exact", "ipc_run_batch_exact"]
 
 
 class Params(C.Structure):
@@ -105,6 +107,11 @@ class ExactResumeReport(C.Structure):
                 ("changed", C.c_int), ("subproblems", C.c_int), ("capped", C.c_int), ("steps", C.c_longlong)]
 
 
+class BatchExactReport(C.Structure):
+    _fields_ = [("runs", C.c_int), ("chunks", C.c_int), ("searched_runs", C.c_int), ("proven_runs", C.c_int),
+                ("set_launches", C.c_int), ("set_host_waits", C.c_int)]
+
+
 CELL_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("lo", "<i4"), ("hi", "<i4"), ("max_chi2", "<f8"),
                        ("chi2_total", "<f8"), ("iterations", "<i4"), ("tries", "<i4"), ("flags", "<i4"),
                        ("evals", "<i4")])
@@ -163,6 +170,9 @@ def load():
     lib.ipc_set_max_exact_resume.argtypes = [vp, vp, ip, vp, C.POINTER(ExactResumeReport), vp]
     lib.ipc_run_online_exact.argtypes = [vp, vp, vp, vp, C.POINTER(OnlineReport), C.POINTER(ExactResumeReport)]
     lib.ipc_online_exact_state.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
+    if hasattr(lib, "ipc_run_batch_exact"):            # (an A/B library of an older build lacks them)
+        lib.ipc_set_max_batch_exact.argtypes = [vp, ip, vp, vp, vp, vp, vp, vp, vp, C.POINTER(BatchExactReport), vp]
+        lib.ipc_run_batch_exact.argtypes = [vp, ip, vp, vp, vp, vp, vp, vp, C.POINTER(BatchReport), vp, C.POINTER(BatchExactReport)]
     lib.ipc_run_sharded.argtypes =[C.POINTER(vp), ip, vp, vp]
     lib.ipc_run_set_only.argtypes = [vp, vp, C.POINTER(ip)]
     lib.ipc_cell_count.argtypes = [vp, C.POINTER(ip)]

@@ -222,6 +222,32 @@ class IPC:
         mo = np.concatenate([[0], np.cumsum(mats)])
         return [bits[mo[q]:mo[q + 1]].reshape(sizes[q], -1) for q in range(len(runs))], accs, report
 
+    def run_batch_exact(self, runs, want_bits=False):
+        """ipc_run_batch_exact: run_batch(), and per run the multi-start and the exact set as well: entry r is what run_exact()
+        returns on a fresh engine given those candidates in that order.  Returns (list of accepted [N_r] uint8, list of
+        multistart, list of greedy -- run_batch()'s sets --, list of exact report dicts, batch report dict, batch-exact report
+        dict), with want_bits the list of bits [N_r, words_r] uint64 in front.  getMaxConsensusSet() is left as it was."""
+        runs = [np.ascontiguousarray(r, dtype=np.int32).reshape(-1) for r in runs]
+        sizes = [int(r.shape[0]) for r in runs]
+        offsets = np.zeros(len(runs) + 1, dtype=np.int32)
+        offsets[1:] = np.cumsum(sizes)
+        members = np.ascontiguousarray(np.concatenate(runs) if runs else np.zeros(0), dtype=np.int32)
+        mats = [n * ((n + 63) // 64) for n in sizes]
+        acc, ms, greedy = (np.zeros(max(int(offsets[-1]), 1), dtype=np.uint8) for _ in range(3))
+        bits = np.zeros(max(sum(mats), 1), dtype=np.uint64) if want_bits else None
+        reps = (capi.ExactReport * max(len(runs), 1))()
+        r, x = capi.BatchReport(), capi.BatchExactReport()
+        capi.check(self.lib.ipc_run_batch_exact(self.h, len(runs), _p(offsets), _p(members), _p(bits) if want_bits else None, _p(greedy),
+                                                _p(ms), _p(acc), C.byref(r), C.cast(reps, C.c_void_p), C.byref(x)))
+        cut = lambda a: [a[offsets[q]:offsets[q + 1]] for q in range(len(runs))]
+        reports = [{k: getattr(reps[q], k) for k, _ in capi.ExactReport._fields_} for q in range(len(runs))]
+        out = (cut(acc), cut(ms), cut(greedy), reports, {k: getattr(r, k) for k, _ in capi.BatchReport._fields_},
+               {k: getattr(x, k) for k, _ in capi.BatchExactReport._fields_})
+        if not want_bits:
+            return out
+        mo = np.concatenate([[0], np.cumsum(mats)])
+        return ([bits[mo[q]:mo[q + 1]].reshape(sizes[q], -1) for q in range(len(runs))],) + out
+
     # ---- multi-start set maximisation: the greedy from every live seed, the largest set ----
     def run_multistart(self, want_bits=False):
         """ipc_run_multistart: solve and assemble as run(), then the greedy set of run() AND the multi-start set from the one
@@ -345,6 +371,20 @@ class IPC:
         r = capi.ExactReport()
         capi.check(self.lib.ipc_set_max_exact(self.h, C.c_void_p(d_bits_ptr), C.c_void_p(d_accepted_ptr), C.byref(r), C.c_void_p(stream)))
         return {k: getattr(r, k) for k, _ in capi.ExactReport._fields_}
+
+    def set_max_batch_exact(self, run_n, order, d_bits_ptr, d_accepted_ptr, d_multistart_ptr=0, d_greedy_ptr=0, stream=0):
+        """ipc_set_max_batch_exact on device pointers: run_n [R] and order (the runs' processing orders back to back) are host
+        arrays.  Blocks until the search is over; returns (list of exact report dicts, batch-exact report dict)."""
+        run_n = np.ascontiguousarray(run_n, dtype=np.int32).reshape(-1)
+        order = np.ascontiguousarray(order, dtype=np.int32).reshape(-1)
+        reps = (capi.ExactReport * max(len(run_n), 1))()
+        x = capi.BatchExactReport()
+        opt = lambda p: C.c_void_p(p) if p else None
+        capi.check(self.lib.ipc_set_max_batch_exact(self.h, len(run_n), _p(run_n), _p(order), C.c_void_p(d_bits_ptr), opt(d_greedy_ptr),
+                                                    opt(d_multistart_ptr), C.c_void_p(d_accepted_ptr), C.cast(reps, C.c_void_p), C.byref(x),
+                                                    C.c_void_p(stream)))
+        return ([{k: getattr(reps[q], k) for k, _ in capi.ExactReport._fields_} for q in range(len(run_n))],
+                {k: getattr(x, k) for k, _ in capi.BatchExactReport._fields_})
 
     def set_max_exact_resume(self, d_bits_ptr, first, d_accepted_ptr, stream=0):
         """ipc_set_max_exact_resume on device pointers; blocks until the search is over and returns the report as a dict."""

@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <cstdarg>
 #include <cstdlib>
 #include <utility>
@@ -760,6 +761,7 @@ static hipError_t launch_se3_lds(int nl, int idx, int n, hipStream_t st, const S
 }
 
 struct BatchRun;                                       // (batch_kernels.hpp)
+struct BxRun; struct BxOpen;                           // (batch_exact_kernels.hpp)
 struct ipc_engine {
     // The engine's one stream of its own.  FIRST member, so that it dies LAST: the solvers below wait for their last launch
     // on it when they die, and every buffer and event goes before the stream does.
@@ -894,6 +896,18 @@ struct ipc_engine {
         unsigned* steps() const { return (unsigned*)vec.part(d_vec, 2); }
     } ex;
     unsigned ex_step_cap = 1u << 20;                   // IPC_EXACT_STEP_CAP: steps after which a subproblem gives up
+    // The sets of a batch (ipc_set_max_batch_exact, ipc_run_batch_exact), for a chunk of runs: descriptors, open
+    // runs and info words per run (batch_exact_kernels.hpp), the compact matrices (words), eight int vectors per run (order,
+    // live, pos, sz, flag, size, steps, the greedy's live list), ipc_run_batch_exact's multi-start and accepted bytes, the
+    // subproblem counter and a pinned staging buffer.  The stacks and the cliques of the search are those of `ex`.
+    struct BatchExactScratch {
+        DevBuf<BxRun> d_runs; DevBuf<BxOpen> d_open; DevBuf<int> d_info; ScratchCap runs;
+        DevBuf<unsigned long long> d_P; ScratchCap mat;
+        DevBuf<int> d_vec; ScratchCap vec;             // d_vec [8][vec]
+        DevBuf<unsigned char> d_ms, d_acc; ScratchCap out;
+        DevBuf<int> d_counter;
+        PinnedBuf<unsigned long long> h_stage; ScratchCap stage;            // in 8-byte words
+    } bx;
     // ipc_run_online_exact holds its set in d_on_exact [on_ccap] (sized and moved with the online storage), proven over the
     // first on_ex_cov candidates.
     DevBuf<unsigned char> d_on_exact;
@@ -1752,6 +1766,7 @@ __device__ __forceinline__ int slot_of_cell(const unsigned* slot_off, int nslots
 #include "multistart_kernels.hpp"
 #include "exact_kernels.hpp"
 #include "exact_resume_kernels.hpp"
+#include "batch_exact_kernels.hpp"
 // Failed cells -> list (host-driven Levenberg retry, rare); borderline cells -> the compact list of their slot (lit_cells /
 // lit_idx at the slot's own offset: a slot has room for all of its cells), counted per slot in recount[0 .. nslots).
 __global__ void k_collect_failed(int ncells, const int4* meta, const double* chi, const int2* cells, double fast_th,
@@ -2402,14 +2417,16 @@ static long long exact_steps(int lo, int hi) { return (long long)(((unsigned lon
 // The workspace of a search from `roots` roots, `levels` deep, over n live candidates: the wave pool's stacks and a clique per
 // root.  What it lacks is refused beyond a quarter of the free memory (`who` and `what` as the caller words it) before it grows.
 struct ExactSearch { int levels, level_words; size_t slice_words; dim3 grid, block; };
-static int exact_workspace(ipc_engine* h, int roots, int n, int words, int levels, const char* who, const char* what, ExactSearch& S)
+// (exact_workspace_for: the same with the level width and the clique entries given -- the batch's search, whose roots belong to
+// runs of different depths.)
+static int exact_workspace_for(ipc_engine* h, int roots, int level_words, int levels, size_t need_clq, const char* who, const char* what,
+                               ExactSearch& S)
 {
     auto& x = h->ex;
-    const int level_words = 64 * (words <= 64 ? 1 : 2) + (n + 3) / 4 + 1;
     const size_t slice_words = (size_t)levels * level_words + (size_t)(levels + 1) / 2;
     int pool = std::min(kExPool, (roots + kExWaves - 1) / kExWaves * kExWaves);
     while (pool > kExPoolFloor && pool * slice_words * 8 > kExPoolBytes) pool /= 2;
-    const size_t need_ws = pool * slice_words, need_clq = (size_t)roots * levels;
+    const size_t need_ws = pool * slice_words;
     if (need_ws > x.ws.size() || need_clq > x.clq.size()) {
         size_t mem_free = 0, mem_total = 0;
         HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
@@ -2422,6 +2439,10 @@ static int exact_workspace(ipc_engine* h, int roots, int n, int words, int level
     HIPCHK(x.clq.grow(need_clq, sized(x.d_clq, need_clq)));
     S = ExactSearch{levels, level_words, slice_words, dim3(pool / kExWaves), dim3(64 * kExWaves)};
     return IPC_OK;
+}
+static int exact_workspace(ipc_engine* h, int roots, int n, int words, int levels, const char* who, const char* what, ExactSearch& S)
+{
+    return exact_workspace_for(h, roots, 64 * (words <= 64 ? 1 : 2) + (n + 3) / 4 + 1, levels, (size_t)roots * levels, who, what, S);
 }
 
 // The multi-start set into d_accepted, UB0, then -- unless that already closes the bracket -- the search and the pick.  Blocks the
@@ -2923,34 +2944,235 @@ extern "C" int ipc_run_sweep(ipc_engine_t* h, int n_th, const double* fast_th, c
 }
 
 // ------------------------------------------------------------------------------------------
+// the sets of a batch: the multi-start and the exact set of every run of a chunk in one launch sequence
+// ------------------------------------------------------------------------------------------
+constexpr int kBxMaxRuns = 65535;                      // the run is the y (or x) dimension of a grid
+
+// scratch for a chunk of `runs` runs with `mat` matrix words and `vec` candidates in all; `outputs`: ipc_run_batch_exact's bytes
+static int ensure_batch_exact_scratch(ipc_engine* h, size_t runs, size_t mat, size_t vec, bool outputs)
+{
+    auto& x = h->bx;
+    HIPCHK(x.runs.grow(runs, sized(x.d_runs, runs), sized(x.d_open, runs), sized(x.d_info, kBxInfo * runs)));
+    HIPCHK(x.mat.grow(mat, sized(x.d_P, mat)));
+    HIPCHK(x.vec.grow(vec, sized(x.d_vec, 8 * vec)));
+    if (outputs) HIPCHK(x.out.grow(vec, sized(x.d_ms, vec), sized(x.d_acc, vec)));
+    if (!x.d_counter) HIPCHK(x.d_counter.alloc(1));
+    const size_t stage = runs * (sizeof(BxRun) + sizeof(BxOpen)) / 8 + (vec * sizeof(int) + 7) / 8;
+    HIPCHK(x.stage.grow(stage, sized(x.h_stage, stage)));
+    return IPC_OK;
+}
+// the parts of the pinned staging buffer, for a call whose largest chunk has `runs` runs
+static BxRun* bx_stage_runs(ipc_engine* h) { return (BxRun*)(unsigned long long*)h->bx.h_stage; }
+static BxOpen* bx_stage_open(ipc_engine* h, size_t runs) { return (BxOpen*)((unsigned long long*)h->bx.h_stage + runs * sizeof(BxRun) / 8); }
+static int* bx_stage_order(ipc_engine* h, size_t runs) { return (int*)((unsigned long long*)h->bx.h_stage + runs * (sizeof(BxRun) + sizeof(BxOpen)) / 8); }
+
+struct BxTotals { int searched = 0, proven = 0, launches = 0, waits = 0; };
+
+// The set stage of one chunk: n runs whose descriptors stand in bx_stage_runs (the scratch is there: ensure_batch_exact_scratch
+// for `cap_runs` runs), `nvec` candidates in all, the largest run `max_n`; matrices and orders on the device at the descriptors'
+// offsets.  d_greedy and d_ms may be NULL.  One launch sequence, the host waits once for every run's (n, LB, UB0) and -- if
+// some bracket is open -- once more behind the search.
+static int batch_exact_stage(ipc_engine* h, hipStream_t st, const char* who, int n, size_t cap_runs, size_t nvec, int max_n,
+                             const unsigned long long* d_bits, const int* d_order, uint8_t* d_greedy, uint8_t* d_ms, uint8_t* d_acc,
+                             ipc_exact_report_t* reports, BxTotals& tot)
+{
+    auto& x = h->bx;
+    const BxRun* s_runs = bx_stage_runs(h);
+    BxOpen* s_open = bx_stage_open(h, cap_runs);
+    int* live = x.vec.part(x.d_vec, 1); int* pos = x.vec.part(x.d_vec, 2); int* sz = x.vec.part(x.d_vec, 3);
+    int* flag = x.vec.part(x.d_vec, 4); int* size = x.vec.part(x.d_vec, 5); unsigned* steps = (unsigned*)x.vec.part(x.d_vec, 6);
+    int* glive = x.vec.part(x.d_vec, 7);
+    const BxRun* runs = x.d_runs;
+    const unsigned long long* P = x.d_P;
+    const int max_words = (max_n + 63) / 64;
+    const bool wide = max_n > 4096;                      // two words of a row per lane
+    HIPCHK(hipMemcpyAsync(x.d_runs, s_runs, sizeof(BxRun) * n, hipMemcpyHostToDevice, st));
+    if (d_greedy) {
+        hipLaunchKernelGGL(k_bx_set_max, dim3(n), dim3(1024), sizeof(unsigned long long) * max_words, st, runs, d_order, d_bits, d_greedy, glive);
+        ++tot.launches;
+    }
+    const dim3 grid((max_n + kMsWaves - 1) / kMsWaves, n), block(64 * kMsWaves);
+    hipLaunchKernelGGL(k_bx_live, dim3(n), dim3(1024), 0, st, runs, d_order, d_bits, live, pos, (int*)x.d_info);
+    hipLaunchKernelGGL(k_bx_compact, grid, block, 0, st, runs, d_bits, (const int*)live, (const int*)x.d_info, (unsigned long long*)x.d_P);
+    if (wide) hipLaunchKernelGGL(k_bx_greedy<2>, grid, block, 0, st, runs, P, (const int*)x.d_info, sz);
+    else hipLaunchKernelGGL(k_bx_greedy<1>, grid, block, 0, st, runs, P, (const int*)x.d_info, sz);
+    hipLaunchKernelGGL(k_bx_ms_pick, dim3(n), dim3(1024), sizeof(unsigned long long) * max_words, st, runs, P, (const int*)live, (const int*)sz,
+                       (int*)x.d_info, d_acc);
+    if (wide) hipLaunchKernelGGL(k_bx_bound<2>, dim3(n), dim3(64), 0, st, runs, P, (int*)x.d_info);
+    else hipLaunchKernelGGL(k_bx_bound<1>, dim3(n), dim3(64), 0, st, runs, P, (int*)x.d_info);
+    tot.launches += 5;
+    HIPCHK(hipGetLastError());
+    if (d_ms) HIPCHK(hipMemcpyAsync(d_ms, d_acc, nvec, hipMemcpyDeviceToDevice, st));       // (before the pick rewrites a run's set)
+    HIPCHK(hipStreamSynchronize(st));
+    ++tot.waits;
+    std::vector<int> info((size_t)n * kBxInfo);
+    HIPCHK(hipMemcpy(info.data(), x.d_info, sizeof(int) * info.size(), hipMemcpyDeviceToHost));
+    // the open runs, their subproblems in one numbering, their cliques back to back
+    int n_open = 0, total = 0, open_n = 0, open_levels = 0;
+    size_t clq = 0;
+    for (int r = 0; r < n; ++r) {
+        const int* in = &info[(size_t)r * kBxInfo];
+        const int nl = in[0], lb = in[1], ub0 = in[4];
+        if (lb >= ub0) continue;
+        const int levels = std::min(ub0, nl);
+        s_open[n_open++] = BxOpen{r, total, levels, 0, (long long)clq};
+        total += nl;
+        clq += (size_t)nl * levels;
+        open_n = std::max(open_n, nl);
+        open_levels = std::max(open_levels, levels);
+    }
+    if (n_open) {
+        ExactSearch S;
+        if (int rc = exact_workspace_for(h, total, 64 * (wide ? 2 : 1) + (open_n + 3) / 4 + 1, open_levels, clq, who,
+                                         "subproblems of the chunk's open runs", S)) return rc;
+        const BxOpen* open = x.d_open;
+        HIPCHK(hipMemcpyAsync(x.d_open, s_open, sizeof(BxOpen) * n_open, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(x.d_counter, 0, sizeof(int), st));
+        if (wide)
+            hipLaunchKernelGGL(k_bx_search<2>, S.grid, S.block, 0, st, n_open, total, S.level_words, S.slice_words, h->ex_step_cap, runs, open, P,
+                               (const int*)x.d_info, (int*)x.d_counter, (unsigned long long*)h->ex.d_ws, flag, size, steps, (unsigned short*)h->ex.d_clq);
+        else
+            hipLaunchKernelGGL(k_bx_search<1>, S.grid, S.block, 0, st, n_open, total, S.level_words, S.slice_words, h->ex_step_cap, runs, open, P,
+                               (const int*)x.d_info, (int*)x.d_counter, (unsigned long long*)h->ex.d_ws, flag, size, steps, (unsigned short*)h->ex.d_clq);
+        hipLaunchKernelGGL(k_bx_pick, dim3(n_open), dim3(1024), 0, st, runs, open, (const int*)live, (const int*)flag, (const int*)size,
+                           (const unsigned*)steps, (const unsigned short*)h->ex.d_clq, (int*)x.d_info, d_acc);
+        tot.launches += 2;
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+        ++tot.waits;
+        HIPCHK(hipMemcpy(info.data(), x.d_info, sizeof(int) * info.size(), hipMemcpyDeviceToHost));
+    }
+    tot.searched += n_open;
+    for (int r = 0; r < n; ++r) {
+        const int* in = &info[(size_t)r * kBxInfo];
+        ipc_exact_report_t rep{};
+        rep.live = in[0]; rep.multistart_size = in[1]; rep.size = in[1]; rep.upper_bound = in[4]; rep.proven = in[1] >= in[4] ? 1 : 0;
+        if (!rep.proven) {
+            rep.subproblems = in[kBxEx + 4]; rep.capped = in[kBxEx + 5];
+            rep.steps = exact_steps(in[kBxEx + 6], in[kBxEx + 7]);
+            if (rep.capped == 0) { rep.proven = 1; rep.size = rep.upper_bound = in[kBxEx + 2]; }
+        }
+        tot.proven += rep.proven;
+        if (reports) reports[r] = rep;
+    }
+    return IPC_OK;
+}
+
+extern "C" int ipc_set_max_batch_exact(ipc_engine_t* h, int n_runs, const int* run_n, const int* order, const uint64_t* d_bits,
+                                       uint8_t* d_greedy, uint8_t* d_multistart, uint8_t* d_accepted, ipc_exact_report_t* reports,
+                                       ipc_batch_exact_report_t* report, void* stream)
+{
+    if (!h || !run_n || !order || !d_bits || !d_accepted) return fail(IPC_ERR_ARG, "ipc_set_max_batch_exact: NULL argument");
+    if (n_runs < 1) return fail(IPC_ERR_ARG, "ipc_set_max_batch_exact: %d runs (need >= 1)", n_runs);
+    size_t nvec = 0, mat = 0;
+    int max_n = 0;
+    for (int r = 0; r < n_runs; ++r) {
+        if (run_n[r] < 1) return fail(IPC_ERR_ARG, "ipc_set_max_batch_exact: run %d has %d candidates (need >= 1)", r, run_n[r]);
+        nvec += (size_t)run_n[r];
+        mat += (size_t)run_n[r] * ((run_n[r] + 63) / 64);
+        max_n = std::max(max_n, run_n[r]);
+    }
+    {
+        std::vector<unsigned char> seen((size_t)max_n);
+        size_t off = 0;
+        for (int r = 0; r < n_runs; off += (size_t)run_n[r], ++r) {
+            std::fill(seen.begin(), seen.begin() + run_n[r], 0);
+            for (int k = 0; k < run_n[r]; ++k) {
+                const int c = order[off + k];
+                if (c < 0 || c >= run_n[r] || seen[c])
+                    return fail(IPC_ERR_ARG, "ipc_set_max_batch_exact: the order of run %d is not a permutation of 0..%d (entry %d: %d)", r,
+                                run_n[r] - 1, k, c);
+                seen[c] = 1;
+            }
+        }
+    }
+    for (int r = 0; r < n_runs; ++r)
+        if (run_n[r] > kExLimitN)
+            return fail(IPC_ERR_LIMIT, "ipc_set_max_batch_exact: run %d with N=%d exceeds %d candidates", r, run_n[r], kExLimitN);
+    if (n_runs > kBxMaxRuns) return fail(IPC_ERR_LIMIT, "ipc_set_max_batch_exact: %d runs exceed %d", n_runs, kBxMaxRuns);
+    if (nvec > (size_t)INT_MAX) return fail(IPC_ERR_LIMIT, "ipc_set_max_batch_exact: %zu candidates in all exceed the 32-bit offsets", nvec);
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->own_stream;
+    if (int rc = matrix_mode_enter(h, st)) return rc;
+    if (int rc = ensure_batch_exact_scratch(h, (size_t)n_runs, mat, nvec, false)) return rc;
+    BxRun* s_runs = bx_stage_runs(h);
+    int* s_order = bx_stage_order(h, (size_t)n_runs);
+    {
+        size_t v = 0, m = 0;
+        for (int r = 0; r < n_runs; ++r) {
+            const int words = (run_n[r] + 63) / 64;
+            s_runs[r] = BxRun{run_n[r], words, (int)v, r * kBxInfo, (long long)m, (long long)m};
+            v += (size_t)run_n[r];
+            m += (size_t)run_n[r] * words;
+        }
+    }
+    std::copy(order, order + nvec, s_order);
+    int* d_order = h->bx.vec.part(h->bx.d_vec, 0);
+    HIPCHK(hipMemcpyAsync(d_order, s_order, sizeof(int) * nvec, hipMemcpyHostToDevice, st));
+    BxTotals tot;
+    if (int rc = batch_exact_stage(h, st, "ipc_set_max_batch_exact", n_runs, (size_t)n_runs, nvec, max_n, (const unsigned long long*)d_bits,
+                                   (const int*)d_order, d_greedy, d_multistart, d_accepted, reports, tot)) return rc;
+    if (report) *report = ipc_batch_exact_report_t{n_runs, 1, tot.searched, tot.proven, tot.launches, tot.waits};
+    return IPC_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // Monte-Carlo batch: the cells solved once, assembled into many candidate lists
 // ------------------------------------------------------------------------------------------
+// ipc_run_batch, and -- with `ex` -- ipc_run_batch_exact: the same call whose chunks also hold the set stage's
+// scratch and end with batch_exact_stage on the chunk's device matrices.
+struct BatchExactOut { uint8_t* multistart_out; uint8_t* accepted_out; ipc_exact_report_t* reports; ipc_batch_exact_report_t* report; };
+static int run_batch_impl(ipc_engine* h, const char* who, int n_runs, const int* run_offsets, const int* members, uint64_t* bits_out,
+                          uint8_t* accepted_out, ipc_batch_report_t* report, const BatchExactOut* ex);
+
 extern "C" int ipc_run_batch(ipc_engine_t* h, int n_runs, const int* run_offsets, const int* members, uint64_t* bits_out,
                              uint8_t* accepted_out, ipc_batch_report_t* report)
 {
-    if (!h) return fail(IPC_ERR_ARG, "ipc_run_batch: NULL handle");
-    if (n_runs < 1) return fail(IPC_ERR_ARG, "ipc_run_batch: %d runs (need >= 1)", n_runs);
-    if (!run_offsets || !members) return fail(IPC_ERR_ARG, "ipc_run_batch: run_offsets or members is NULL");
-    if (h->N <= 0) return fail(IPC_ERR_STATE, "ipc_run_batch: no candidates set");
+    return run_batch_impl(h, "ipc_run_batch", n_runs, run_offsets, members, bits_out, accepted_out, report, nullptr);
+}
+
+extern "C" int ipc_run_batch_exact(ipc_engine_t* h, int n_runs, const int* run_offsets, const int* members, uint64_t* bits_out,
+                                   uint8_t* greedy_out, uint8_t* multistart_out, uint8_t* accepted_out, ipc_batch_report_t* batch_report,
+                                   ipc_exact_report_t* reports, ipc_batch_exact_report_t* report)
+{
+    const BatchExactOut ex{multistart_out, accepted_out, reports, report};
+    return run_batch_impl(h, "ipc_run_batch_exact", n_runs, run_offsets, members, bits_out, greedy_out, batch_report, &ex);
+}
+
+static int run_batch_impl(ipc_engine* h, const char* who, int n_runs, const int* run_offsets, const int* members, uint64_t* bits_out,
+                          uint8_t* accepted_out, ipc_batch_report_t* report, const BatchExactOut* ex)
+{
+    if (!h) return fail(IPC_ERR_ARG, "%s: NULL handle", who);
+    if (n_runs < 1) return fail(IPC_ERR_ARG, "%s: %d runs (need >= 1)", who, n_runs);
+    if (!run_offsets || !members) return fail(IPC_ERR_ARG, "%s: run_offsets or members is NULL", who);
+    if (h->N <= 0) return fail(IPC_ERR_STATE, "%s: no candidates set", who);
     const int N = h->N, R = n_runs, mw = (R + 63) / 64;
     for (int r = 0; r < R; ++r) {
         const int a = run_offsets[r], b = run_offsets[r + 1];
-        if (a < 0 || b <= a) return fail(IPC_ERR_ARG, "ipc_run_batch: run %d is empty (offsets %d .. %d)", r, a, b);
+        if (a < 0 || b <= a) return fail(IPC_ERR_ARG, "%s: run %d is empty (offsets %d .. %d)", who, r, a, b);
         for (int k = a; k < b; ++k) {
-            if (members[k] < 0 || members[k] >= N) return fail(IPC_ERR_ARG, "ipc_run_batch: run %d names candidate %d outside 0..%d", r, members[k], N - 1);
-            if (k > a && members[k] <= members[k - 1]) return fail(IPC_ERR_ARG, "ipc_run_batch: the members of run %d are not strictly increasing", r);
+            if (members[k] < 0 || members[k] >= N) return fail(IPC_ERR_ARG, "%s: run %d names candidate %d outside 0..%d", who, r, members[k], N - 1);
+            if (k > a && members[k] <= members[k - 1]) return fail(IPC_ERR_ARG, "%s: the members of run %d are not strictly increasing", who, r);
         }
     }
-    if (run_offsets[0] != 0) return fail(IPC_ERR_ARG, "ipc_run_batch: run_offsets[0] = %d (need 0)", run_offsets[0]);
+    if (run_offsets[0] != 0) return fail(IPC_ERR_ARG, "%s: run_offsets[0] = %d (need 0)", who, run_offsets[0]);
     // A run costs an upper triangle and a matrix, the accepted bytes, five int vectors, its local-index map and its descriptor.
     auto run_n = [&](int r) { return run_offsets[r + 1] - run_offsets[r]; };
     auto run_bytes = [&](int r) {
         const size_t n = (size_t)run_n(r), words = (n + 63) / 64;
-        return 2 * n * words * sizeof(unsigned long long) + n * (1 + 5 * sizeof(int)) + (size_t)N * sizeof(int) + sizeof(BatchRun);
+        // ... and with the sets: the compact matrix, eight more int vectors, two more byte vectors, room for a clique per
+        // subproblem (at most n members of 16 bits each), its info words, descriptor and open-run entry
+        const size_t sets = ex ? n * words * sizeof(unsigned long long) + n * (2 + 8 * sizeof(int)) + n * n * sizeof(unsigned short) +
+                                     kBxInfo * sizeof(int) + sizeof(BxRun) + sizeof(BxOpen)
+                               : 0;
+        return 2 * n * words * sizeof(unsigned long long) + n * (1 + 5 * sizeof(int)) + (size_t)N * sizeof(int) + sizeof(BatchRun) + sets;
     };
     for (int r = 0; r < R; ++r)
         if (!mask_fits_lds(run_n(r)))
-            return fail(IPC_ERR_LIMIT, "ipc_run_batch: run %d with %d candidates exceeds the LDS-resident mask", r, run_n(r));
+            return fail(IPC_ERR_LIMIT, "%s: run %d with %d candidates exceeds the LDS-resident mask", who, r, run_n(r));
+    if (ex)
+        for (int r = 0; r < R; ++r)
+            if (run_n(r) > kExLimitN) return fail(IPC_ERR_LIMIT, "%s: run %d with N=%d exceeds %d candidates", who, r, run_n(r), kExLimitN);
     HIPCHK(hipSetDevice(h->device));
     // Chunks of consecutive runs: as many as fit a quarter of the free memory (the scratch the engine holds counts as free: a
     // growth replaces it), capped by IPC_BATCH_CHUNK runs and IPC_BATCH_BUDGET bytes.  Nothing is allocated if a run fits none.
@@ -2958,7 +3180,8 @@ extern "C" int ipc_run_batch(ipc_engine_t* h, int n_runs, const int* run_offsets
     {
         size_t mem_free = 0, mem_total = 0;
         HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
-        const size_t held = 2 * h->bt.mat.size() * sizeof(unsigned long long) + h->bt.vec.size() * (1 + 5 * sizeof(int)) + h->bt.loc.size() * sizeof(int);
+        size_t held = 2 * h->bt.mat.size() * sizeof(unsigned long long) + h->bt.vec.size() * (1 + 5 * sizeof(int)) + h->bt.loc.size() * sizeof(int);
+        if (ex) held += h->bx.mat.size() * sizeof(unsigned long long) + h->bx.vec.size() * 8 * sizeof(int) + h->bx.out.size() * 2 + h->ex.clq.size() * sizeof(unsigned short);
         budget = (mem_free + held) / 4;
         if (h->batch_budget) budget = std::min(budget, h->batch_budget);
     }
@@ -2968,10 +3191,11 @@ extern "C" int ipc_run_batch(ipc_engine_t* h, int n_runs, const int* run_offsets
         for (int r = 0; r < R; ++r) {
             const size_t need = run_bytes(r);
             if (need > budget)
-                return fail(IPC_ERR_LIMIT, "ipc_run_batch: run %d with %d candidates needs %zu KB of scratch, the budget of a chunk is %zu KB",
+                return fail(IPC_ERR_LIMIT, "%s: run %d with %d candidates needs %zu KB of scratch, the budget of a chunk is %zu KB", who,
                             r, run_n(r), need >> 10, budget >> 10);
             const int in_chunk = r - chunk_first.back();
-            if (in_chunk > 0 && (used + need > budget || (h->batch_chunk > 0 && in_chunk >= h->batch_chunk))) { chunk_first.push_back(r); used = 0; }
+            if (in_chunk > 0 && (used + need > budget || (h->batch_chunk > 0 && in_chunk >= h->batch_chunk) ||
+                                 (ex && in_chunk >= kBxMaxRuns))) { chunk_first.push_back(r); used = 0; }
             used += need;
         }
         chunk_first.push_back(R);
@@ -2995,6 +3219,7 @@ extern "C" int ipc_run_batch(ipc_engine_t* h, int n_runs, const int* run_offsets
     HIPCHK(b.runs.grow(need_runs, sized(b.d_runs, need_runs)));
     HIPCHK(b.memb.grow(need_memb, sized(b.d_memb, need_memb)));
     if (!b.d_sep) HIPCHK(b.d_sep.alloc(1));
+    if (ex) { if (int rc = ensure_batch_exact_scratch(h, need_runs, need_mat, need_vec, true)) return rc; }
     // the pinned staging, in 8-byte words: the membership words, later a chunk's descriptors, orders, members and maps
     const size_t stage_runs = (need_runs * sizeof(BatchRun) + 7) / 8, stage_vec = (need_vec * sizeof(int) + 7) / 8;
     const size_t need_stage = std::max(need_memb, stage_runs + 2 * stage_vec + (need_loc * sizeof(int) + 7) / 8);
@@ -3031,6 +3256,7 @@ extern "C" int ipc_run_batch(ipc_engine_t* h, int n_runs, const int* run_offsets
     }
     std::vector<int> locmap((size_t)N);
     size_t bits_done = 0;                                // words of bits_out written so far
+    BxTotals bx_tot;
     for (int q = 0; q < n_chunks; ++q) {
         const int c0 = chunk_first[q], n = chunk_first[q + 1] - c0, v0 = run_offsets[c0];
         const size_t nvec = (size_t)(run_offsets[c0 + n] - v0);
@@ -3043,6 +3269,7 @@ extern "C" int ipc_run_batch(ipc_engine_t* h, int n_runs, const int* run_offsets
         for (int rc = 0; rc < n; ++rc) {
             const int r = c0 + rc, nr = run_n(r), words = (nr + 63) / 64, voff = run_offsets[r] - v0;
             s_runs[rc] = BatchRun{nr, words, voff, 0, (long long)mat};
+            if (ex) bx_stage_runs(h)[rc] = BxRun{nr, words, voff, rc * kBxInfo, (long long)mat, (long long)mat};
             mat += (size_t)nr * words;
             max_n = std::max(max_n, nr);
             int* loc = s_loc + (size_t)rc * N;
@@ -3071,13 +3298,20 @@ extern "C" int ipc_run_batch(ipc_engine_t* h, int n_runs, const int* run_offsets
         hipLaunchKernelGGL(k_batch_set_max, dim3(n), dim3(1024), sizeof(unsigned long long) * max_words, st, (const BatchRun*)h->bt.d_runs,
                            (const int*)d_order_r, (const unsigned long long*)h->bt.d_bits, h->bt.d_acc, d_live);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(st));                // (the staging buffer is free for the next chunk when this returns)
+        if (ex) {                                        // the sets of the chunk's runs, before the next chunk overwrites the matrices
+            if (int rc = batch_exact_stage(h, st, who, n, need_runs, nvec, max_n, (const unsigned long long*)h->bt.d_bits, (const int*)d_order_r,
+                                           nullptr, h->bx.d_ms, h->bx.d_acc, ex->reports ? ex->reports + c0 : nullptr, bx_tot)) return rc;
+            if (ex->multistart_out) HIPCHK(hipMemcpy(ex->multistart_out + v0, h->bx.d_ms, nvec, hipMemcpyDeviceToHost));
+            if (ex->accepted_out) HIPCHK(hipMemcpy(ex->accepted_out + v0, h->bx.d_acc, nvec, hipMemcpyDeviceToHost));
+        }
+        else HIPCHK(hipStreamSynchronize(st));           // (the staging buffer is free for the next chunk when this returns)
         if (bits_out) HIPCHK(hipMemcpy(bits_out + bits_done, h->bt.d_bits, sizeof(uint64_t) * mat, hipMemcpyDeviceToHost));
         if (accepted_out) HIPCHK(hipMemcpy(accepted_out + v0, h->bt.d_acc, nvec, hipMemcpyDeviceToHost));
         bits_done += mat;
         ++rep.chunks;
     }
     if (report) *report = rep;
+    if (ex && ex->report) *ex->report = ipc_batch_exact_report_t{R, rep.chunks, bx_tot.searched, bx_tot.proven, bx_tot.launches, bx_tot.waits};
     return IPC_OK;
 }
 

@@ -68,6 +68,14 @@ class EngineBackend:
         """The exact set or its bracket (ipc_set_max_exact): accepted [N] uint8; blocks the host, returns the report dict."""
         return self.e.set_max_exact(bits.data_ptr(), accepted.data_ptr(), self._stream())
 
+    def set_max_batch_exact(self, run_n, order, bits, accepted, multistart=None, greedy=None):
+        """The sets of a batch of matrices (ipc_set_max_batch_exact): bits holds the matrices back to back, accepted, multistart
+        and greedy [sum N_r] uint8 with the offsets of `order` (host, the runs' orders back to back); blocks the host, returns
+        (list of exact report dicts, batch-exact report dict)."""
+        return self.e.set_max_batch_exact(run_n, order, bits.data_ptr(), accepted.data_ptr(),
+                                          multistart.data_ptr() if multistart is not None else 0,
+                                          greedy.data_ptr() if greedy is not None else 0, self._stream())
+
     def set_max_exact_resume(self, bits, first, accepted):
         """The exact set resumed from `accepted`, a maximum set of the candidates < first (ipc_set_max_exact_resume): accepted
         [N] uint8, in and out; blocks the host, returns the report dict."""
