@@ -1,7 +1,7 @@
 // Monte-Carlo batch (ipc_run_batch): R candidate lists ("runs") drawn from the engine's list, the union U.  The
 // cells that some run needs are solved once, in union indices, by the engine's own planner rule and cell kernels; these kernels
-// plan them and turn their records into every run's own matrix and consistent set.  Included by engine.hip behind k_plan's
-// constants, assemble_tiles and set_max_rounds, whose tile scheme and round logic the per-run kernels share with
+// plan them and turn their records into every run's own matrix and consistent set.  Included by engine.hip behind BinCaps (cell_plan.hpp),
+// k_plan's constants, assemble_tiles and set_max_rounds, whose tile scheme and round logic the per-run kernels share with
 // k_assemble_delta, k_set_max and the k_sweep_* kernels.
 //
 // memb [N_u][mw], mw = ceil(R / 64): bit r of candidate u's words = u is a member of run r.  A cell (i, j >= i) is needed iff the

@@ -26,7 +26,7 @@
 #include <vector>
 
 #include "../../include/ipc_amd.h"
-#include "cell_kernels.hpp"
+#include "cell_plan.hpp"
 #include "cluster_se2.hpp"
 #include "cluster_se3.hpp"
 #include "cluster_persist.hpp"
@@ -58,11 +58,8 @@ static int fail(int code, const char* fmt, ...)
 extern "C" const char* ipc_last_error(void) { return g_err.c_str(); }
 
 // ------------------------------------------------------------------------------------------
-// kernel variants: (threads per cell, poses per thread); capacity = T*M poses
+// chain-length bins (BinCaps, the plan that fills it: cell_plan.hpp)
 // ------------------------------------------------------------------------------------------
-constexpr int kMaxBins = 32;
-struct BinCaps { int n; int cap[kMaxBins]; };
-
 __device__ __forceinline__ int bin_of(const BinCaps& bc, int L)
 {
     int b = 0;
@@ -595,171 +592,9 @@ __global__ __launch_bounds__(1024) void k_set_max(int N, int words, int stride, 
 // ------------------------------------------------------------------------------------------
 // engine
 // ------------------------------------------------------------------------------------------
-// Chain-length bins: each bin is served by one (W, M) kernel variant.  The policy string
-// (env IPC_SE2_POLICY, default below) lists the variants to use as "WxM" tokens (block kernel, W
-// waves per cell, M poses per lane), "wM" tokens (SE2 wave kernel, one wave per cell, M poses per
-// lane), "pM" tokens (SE2 pair kernel, two waves per cell), "qM" tokens (SE2 quad kernel, four
-// waves per cell) or "kwM" / "kpM" tokens (the kept-trial form of the wave / pair kernel, same capacity and
-// results: DESIGN.md 4.1); a cell goes to the listed variant of
-// smallest capacity 64*W*M that holds it.
-struct BinPlan {
-    BinCaps caps;
-    int variant[kMaxBins];
-    // SE3: variant for a bin with too few cells to fill the GPU (more waves per cell, so the few
-    // cells finish sooner), and the cell count below which it is used
-    int latency_variant[kMaxBins];
-    int latency_below[kMaxBins];
-    // SE2: the bin's kernel is served by its lazy steepest-descent form (same cells, same bits; lazy_sd_serves below)
-    bool lazy_sd[kMaxBins];
-};
-// kwM / kpM where the kept-trial kernel passed its static and its measured gate: not at M = 11, whose
-// kept-trial kernels spill to scratch and run slower than w11 / p11
-static const char* kDefaultPolicy = "w1,w3,kw5,kw7,kw9,w11,w13,kp7,kp9,p11,q7,q9,q11,q13,16x4,16x8,16x16";
-// The lazy steepest-descent kernels (se2_wave_lz.hip / se2_pair_lz.hip, LAZY_SD of se2_wave_solve) are not variants of
-// their own: each computes, bit for bit, what one kernel of the default policy computes, so it has no token, no capacity
-// and no place in a policy string -- a bin whose variant is that kernel is served by the lazy one.  IPC_SE2_LAZY_SD=0
-// (read with the policy) switches the substitution off: every token then launches the kernel it names, which is the A/B
-// partner inside one library; =2 substitutes every M that has a lazy kernel, listed below or not (the bitwise test and
-// the per-bin gate runs reach the unlisted ones that way).  Only the M listed here are substituted by default: the
-// kernels that passed the static gate (tests/test_se2_lazy_sd_loop_mix.py) and the measured one
-// (profiles/se2_lazy_sd_c2_kernel_gate.txt, profiles/se2_lazy_gauge_c2_kernel_gate.txt).
-// Every one of the eight is faster in its bin on the MI355X; lw9 and lp9 are listed since they park the gauge pose in
-// accumulator registers by hand (PARK_GAUGE, se2_wave_cell.hpp: no spilled vector register in any instantiation) and lp7
-// since its "terms formed" flag is a bit of the flags word (SD_BIT: no more spilled scalar registers than kp7); lw13 is
-// held back by its scratch: DESIGN.md 8 has the figures.
-static const int kLazySdWaveM[] = {5, 7, 9, 11};         // for kw5, kw7, kw9, w11 (not 13: w13)
-static const int kLazySdPairM[] = {7, 9, 11};            // for kp7, kp9, p11
-static bool lazy_sd_serves(int variant, bool every)    // every: any M that has a lazy kernel (IPC_SE2_LAZY_SD=2, tests and gate runs)
-{
-    bool wave = false, pair = false;
-    int m = 0;
-    if (variant >= kPairKtVariantBase) { pair = true; m = variant - kPairKtVariantBase; if (m > kLazyKeepTrialMaxM) return false; }
-    else if (variant >= kWaveKtVariantBase) { wave = true; m = variant - kWaveKtVariantBase; if (m > kLazyKeepTrialMaxM) return false; }
-    else if (variant >= kQuadVariantBase) return false;
-    else if (variant >= kPairVariantBase) { pair = true; m = variant - kPairVariantBase; if (m <= kLazyKeepTrialMaxM) return false; }
-    else if (variant >= kWaveVariantBase) { wave = true; m = variant - kWaveVariantBase; if (m <= kLazyKeepTrialMaxM) return false; }
-    if (every) {
-        if (wave) for (int k : kWaveLzM) if (k == m) return true;
-        if (pair) for (int k : kPairLzM) if (k == m) return true;
-        return false;
-    }
-    if (wave) for (int k : kLazySdWaveM) if (k == m) return true;
-    if (pair) for (int k : kLazySdPairM) if (k == m) return true;
-    return false;
-}
 // engine streams + the caller's stream = the runtime's four hardware queues for SE2; the long SE3
 // launches gain a little from a fourth engine stream
 static const int kDefaultSideStreams2 = 7, kDefaultSideStreams3 = 7;      // (round 5: 2 / 3 until the side streams came from the process pool -- at 8 ranks a shard's bins hold fewer cells than the GPU has CUs and only concurrent launches fill it: C2 emulated 6.53x -> 7.07x, one rank unchanged)
-static const char* kDefaultPolicy3 = "w1,w2,w3,w4,w6,w8,g3,g4,g5,g6,g7,g8,g9,g10,16x4";
-static const char* kBlockPolicy3 = "1x1,1x2,1x3,2x2,2x3,4x2,4x4,8x4,8x5,16x4";   // round-1 block kernels only (IPC_SE3_POLICY=block)
-// SE3 variants for thin bins, by capacity (IPC_SE3_LATENCY_POLICY; "none" disables the switch)
-static const char* kDefaultLatencyPolicy3 = "1x1,2x1,4x1,4x2,4x4,8x4,8x5,16x4";
-static bool make_plan(BinPlan& bp, int dim, std::string& err)
-{
-    const char* env = getenv(dim == 2 ? "IPC_SE2_POLICY" : "IPC_SE3_POLICY");
-    std::string pol = env && *env ? env : (dim == 2 ? kDefaultPolicy : kDefaultPolicy3);
-    if (dim == 3 && pol == "block") pol = kBlockPolicy3;
-    const Variant* table = dim == 2 ? kVariants : kVariants3;
-    const int ntable = dim == 2 ? kNumVariants : kNumVariants3;
-    std::vector<std::pair<int, int>> items;          // (cap, variant)
-    size_t pos = 0;
-    while (pos < pol.size()) {
-        size_t e = pol.find(',', pos);
-        if (e == std::string::npos) e = pol.size();
-        int w = 0, m = 0;
-        const std::string tok = pol.substr(pos, e - pos);
-        int v = -1;
-        if (dim == 2 && sscanf(tok.c_str(), "kw%d", &m) == 1) {         // kept-trial wave kernel (before "w%d": a prefix, not a suffix, names it)
-            w = 1;
-            for (int k = 0; k < kNumWaveKtM; ++k) if (kWaveKtM[k] == m) v = kWaveKtVariantBase + m;
-        } else if (dim == 2 && sscanf(tok.c_str(), "kp%d", &m) == 1) {  // kept-trial pair kernel
-            w = 2;
-            for (int k = 0; k < kNumPairKtM; ++k) if (kPairKtM[k] == m) v = kPairKtVariantBase + m;
-        } else if (dim == 2 && sscanf(tok.c_str(), "w%d", &m) == 1) {   // wave kernel, M poses per lane
-            w = 1;
-            for (int k = 0; k < kNumWaveM; ++k) if (kWaveM[k] == m) v = kWaveVariantBase + m;
-        } else if (dim == 2 && sscanf(tok.c_str(), "p%d", &m) == 1) {   // pair kernel, two waves per cell
-            w = 2;
-            for (int k = 0; k < kNumPairM; ++k) if (kPairM[k] == m) v = kPairVariantBase + m;
-        } else if (dim == 2 && sscanf(tok.c_str(), "q%d", &m) == 1) {   // quad kernel, four waves per cell
-            w = 4;
-            for (int k = 0; k < kNumQuadM; ++k) if (kQuadM[k] == m) v = kQuadVariantBase + m;
-        } else if (dim == 3 && (sscanf(tok.c_str(), "w%d", &m) == 1 || sscanf(tok.c_str(), "g%d", &m) == 1)) {
-            w = tok[0] == 'w' ? 1 : 4;                                     // LDS-pose kernel, teams of 1 / 4 waves
-            for (int k = 0; k < kNumLdsVariants3; ++k)
-                if (kLdsVariants3[k].W == w && kLdsVariants3[k].M == m) v = kLdsVariantBase3 + k;
-        } else {
-            if (sscanf(tok.c_str(), "%dx%d", &w, &m) != 2) { err = "bad IPC_SE2_POLICY token"; return false; }
-            for (int k = 0; k < ntable; ++k) if (table[k].W == w && table[k].M == m) v = k;
-        }
-        if (v < 0) { err = "IPC_SE*_POLICY names a variant that is not compiled: " + tok; return false; }
-        items.push_back({64 * w * m, v});
-        pos = e + 1;
-    }
-    std::sort(items.begin(), items.end());
-    if (items.empty() || (int)items.size() > kMaxBins) { err = "IPC_SE2_POLICY: 1..32 variants"; return false; }
-    bp.caps.n = (int)items.size();
-    for (int b = 0; b < kMaxBins; ++b) {
-        bp.caps.cap[b] = b < bp.caps.n ? items[b].first : 0;
-        bp.variant[b] = b < bp.caps.n ? items[b].second : -1;
-        bp.latency_variant[b] = -1;
-        bp.latency_below[b] = 0;
-        bp.lazy_sd[b] = false;
-    }
-    if (dim == 2) {
-        const char* lz = getenv("IPC_SE2_LAZY_SD");
-        if (lz && *lz && strcmp(lz, "0") != 0 && strcmp(lz, "1") != 0 && strcmp(lz, "2") != 0) { err = "IPC_SE2_LAZY_SD: 0, 1 or 2"; return false; }
-        const bool lazy_on = !(lz && *lz == '0'), every = lz && *lz == '2';
-        for (int b = 0; b < bp.caps.n; ++b) bp.lazy_sd[b] = lazy_on && lazy_sd_serves(bp.variant[b], every);
-    }
-    if (dim == 3) {
-        const char* lenv = getenv("IPC_SE3_LATENCY_POLICY");
-        const std::string lpol = lenv && *lenv ? lenv : kDefaultLatencyPolicy3;
-        if (lpol != "none") {
-            size_t lp = 0;
-            std::vector<std::pair<int, int>> lat;       // (cap, variant)
-            while (lp < lpol.size()) {
-                size_t e = lpol.find(',', lp);
-                if (e == std::string::npos) e = lpol.size();
-                int w = 0, m = 0, v = -1;
-                if (sscanf(lpol.substr(lp, e - lp).c_str(), "%dx%d", &w, &m) != 2) { err = "bad IPC_SE3_LATENCY_POLICY token"; return false; }
-                for (int k = 0; k < ntable; ++k) if (table[k].W == w && table[k].M == m) v = k;
-                if (v < 0) { err = "IPC_SE3_LATENCY_POLICY names a variant that is not compiled"; return false; }
-                lat.push_back({64 * w * m, v});
-                lp = e + 1;
-            }
-            std::sort(lat.begin(), lat.end());
-            for (int b = 0; b < bp.caps.n; ++b) {
-                if (bp.variant[b] >= kLdsVariantBase3) continue;             // block variants only
-                const int wt = table[bp.variant[b]].W;
-                for (const auto& lv : lat) {
-                    if (lv.first < bp.caps.cap[b]) continue;
-                    // only a variant with more waves per cell is a latency variant
-                    if (table[lv.second].W > wt) {
-                        bp.latency_variant[b] = lv.second;
-                        bp.latency_below[b] = wt <= 4 ? 4 / wt : 1;      // x CUs at launch time
-                    }
-                    break;
-                }
-            }
-        }
-    }
-    return true;
-}
-
-static hipError_t launch_se3_lds(int nl, int idx, int n, hipStream_t st, const Se3View& P, const int2* cells,
-                                 SolveParams prm, CellOut out, unsigned* counter, int n_cu)
-{
-#define IPC_LCASE(i, WW, MM) case i: return launch_se3_lds_##WW##_##MM(nl, n, st, P, cells, prm, out, counter, n_cu);
-    switch (idx) {
-        IPC_LCASE(0, 1, 1) IPC_LCASE(1, 1, 2) IPC_LCASE(2, 1, 3) IPC_LCASE(3, 1, 4) IPC_LCASE(4, 1, 6) IPC_LCASE(5, 1, 8)
-        IPC_LCASE(6, 4, 2) IPC_LCASE(7, 4, 3) IPC_LCASE(8, 4, 4) IPC_LCASE(9, 4, 5) IPC_LCASE(10, 4, 6) IPC_LCASE(11, 4, 7)
-        IPC_LCASE(12, 4, 8) IPC_LCASE(13, 4, 9) IPC_LCASE(14, 4, 10)
-        default: return hipErrorInvalidValue;
-    }
-#undef IPC_LCASE
-}
-
 struct BatchRun;                                       // (batch_kernels.hpp)
 struct BxRun; struct BxOpen;                           // (batch_exact_kernels.hpp)
 struct ipc_engine {
@@ -1994,24 +1829,10 @@ struct SlotLauncher {
     }
     hipError_t operator()(int b, int nl, int n, const int2* cells, const CellOut& out, hipStream_t ls, unsigned* ctr) const
     {
-        int var = h->plan.variant[b];
-        if (h->plan.latency_variant[b] >= 0 && n < h->plan.latency_below[b] * h->n_cu) var = h->plan.latency_variant[b];
-        if (h->dim == 2 && var == h->plan.variant[b] && h->plan.lazy_sd[b]) {
-            h->lazy_sd_launches.fetch_add(1, std::memory_order_relaxed);
-            const bool pair = var >= kPairKtVariantBase || (var < kWaveKtVariantBase && var >= kPairVariantBase);
-            const int m = var % 100;
-            return pair ? launch_se2_pair_lz(nl, m, n, ls, P, cells, sp, out, ctr, h->n_cu)
-                        : launch_se2_wave_lz(nl, m, n, ls, P, cells, sp, out, ctr, h->n_cu);
-        }
-        if (h->dim == 2)
-            return var >= kPairKtVariantBase ? launch_se2_pair_kt(nl, var - kPairKtVariantBase, n, ls, P, cells, sp, out, ctr, h->n_cu)
-                   : var >= kWaveKtVariantBase ? launch_se2_wave_kt(nl, var - kWaveKtVariantBase, n, ls, P, cells, sp, out, ctr, h->n_cu)
-                   : var >= kQuadVariantBase ? launch_se2_quad(nl, var - kQuadVariantBase, n, ls, P, cells, sp, out, ctr, h->n_cu)
-                   : var >= kPairVariantBase ? launch_se2_pair(nl, var - kPairVariantBase, n, ls, P, cells, sp, out, ctr, h->n_cu)
-                   : var >= kWaveVariantBase ? launch_se2_wave(nl, var - kWaveVariantBase, n, ls, P, cells, sp, out, ctr, h->n_cu)
-                                             : launch_se2_block(nl, var, n, ls, P, cells, sp, out);
-        if (var >= kLdsVariantBase3) return launch_se3_lds(nl, var - kLdsVariantBase3, n, ls, P3, cells, sp, out, ctr, h->n_cu);
-        return launch_se3_block(nl, var, n, ls, P3, cells, sp, out);
+        const CellKernel& k = choose_kernel(h->plan, b, n, h->n_cu);
+        if (is_lazy_sd(k)) h->lazy_sd_launches.fetch_add(1, std::memory_order_relaxed);
+        return h->dim == 2 ? k.se2(nl, k.W, k.M, n, ls, P, cells, sp, out, ctr, h->n_cu)
+                           : k.se3(nl, k.W, k.M, n, ls, P3, cells, sp, out, ctr, h->n_cu);
     }
 };
 

@@ -2,8 +2,7 @@
 #include "se2_group_kernel.hpp"
 
 namespace ipc {
-hipError_t launch_se2_pair(int nl, int M, int n, hipStream_t st, const Se2View& P, const int2* cells, SolveParams prm,
-                           CellOut out, unsigned* counter, int n_cu)
+IPC_CELL_LAUNCHER(launch_se2_pair, Se2View)
 {
 #define IPC_PCASE(MM)                                                                              \
     case MM:                                                                                       \
@@ -13,10 +12,7 @@ hipError_t launch_se2_pair(int nl, int M, int n, hipStream_t st, const Se2View& 
 #ifdef IPC_PAIR_ONLY_M                                 // (tools/maxilp_repro.py: one instantiation, seconds to compile)
         IPC_PCASE(IPC_PAIR_ONLY_M)
 #else
-        IPC_PCASE(5)
-        IPC_PCASE(7)
-        IPC_PCASE(9)
-        IPC_PCASE(11)
+        IPC_SE2_PAIR_M(IPC_PCASE)
 #endif
         default: return hipErrorInvalidValue;
     }

@@ -1,13 +1,12 @@
 // Lazy steepest-descent pair kernels of the SE(2) cell solver: two waves per cell (se2_group_kernel.hpp with W = 2), the
 // instantiations of se2_group_kernel_lz, which form b^T H b, alpha and |h_sd| only in the iterations whose trial loop
 // reads them (LAZY_SD of se2_wave_solve) and otherwise are the kernel the default policy names for that M: kept trial at
-// M = 7, 9 (kpM), re-sweep at M = 11 (p11).  No policy token: engine.hip serves those bins with these kernels
-// (IPC_SE2_LAZY_SD).
+// M = 7, 9 (kpM), re-sweep at M = 11 (p11).  No policy token: the plan serves those bins with these kernels
+// (IPC_SE2_LAZY_SD, cell_plan.hpp).
 #include "se2_group_kernel.hpp"
 
 namespace ipc {
-hipError_t launch_se2_pair_lz(int nl, int M, int n, hipStream_t st, const Se2View& P, const int2* cells, SolveParams prm,
-                              CellOut out, unsigned* counter, int n_cu)
+IPC_CELL_LAUNCHER(launch_se2_pair_lz, Se2View)
 {
 #define IPC_PCASE(MM)                                                                                                  \
     case MM:                                                                                                           \
@@ -17,9 +16,7 @@ hipError_t launch_se2_pair_lz(int nl, int M, int n, hipStream_t st, const Se2Vie
 #ifdef IPC_PAIR_LZ_ONLY_M                              // (tools/isa_loop_mix.py: one instantiation, seconds to compile)
         IPC_PCASE(IPC_PAIR_LZ_ONLY_M)
 #else
-        IPC_PCASE(7)
-        IPC_PCASE(9)
-        IPC_PCASE(11)
+        IPC_SE2_PAIR_LZ_M(IPC_PCASE)
 #endif
         default: return hipErrorInvalidValue;
     }

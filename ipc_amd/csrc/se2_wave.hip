@@ -3,8 +3,7 @@
 #include "se2_wave_kernel.hpp"
 
 namespace ipc {
-hipError_t launch_se2_wave(int nl, int M, int n, hipStream_t st, const Se2View& P, const int2* cells, SolveParams prm,
-                           CellOut out, unsigned* counter, int n_cu)
+IPC_CELL_LAUNCHER(launch_se2_wave, Se2View)
 {
 #define IPC_WCASE(MM)                                                                              \
     case MM:                                                                                       \
@@ -14,13 +13,7 @@ hipError_t launch_se2_wave(int nl, int M, int n, hipStream_t st, const Se2View& 
 #ifdef IPC_WAVE_ONLY_M
         IPC_WCASE(IPC_WAVE_ONLY_M)
 #else
-        IPC_WCASE(1)
-        IPC_WCASE(3)
-        IPC_WCASE(5)
-        IPC_WCASE(7)
-        IPC_WCASE(9)
-        IPC_WCASE(11)
-        IPC_WCASE(13)
+        IPC_SE2_WAVE_M(IPC_WCASE)
 #endif
         default: return hipErrorInvalidValue;
     }

@@ -3,8 +3,7 @@
 #include "se2_wave_kernel.hpp"
 
 namespace ipc {
-hipError_t launch_se2_wave_kt(int nl, int M, int n, hipStream_t st, const Se2View& P, const int2* cells, SolveParams prm,
-                              CellOut out, unsigned* counter, int n_cu)
+IPC_CELL_LAUNCHER(launch_se2_wave_kt, Se2View)
 {
 #define IPC_WCASE(MM)                                                                              \
     case MM:                                                                                       \
@@ -14,10 +13,7 @@ hipError_t launch_se2_wave_kt(int nl, int M, int n, hipStream_t st, const Se2Vie
 #ifdef IPC_WAVE_KT_ONLY_M                              // (tools/isa_loop_mix.py: one instantiation, seconds to compile)
         IPC_WCASE(IPC_WAVE_KT_ONLY_M)
 #else
-        IPC_WCASE(5)
-        IPC_WCASE(7)
-        IPC_WCASE(9)
-        IPC_WCASE(11)
+        IPC_SE2_WAVE_KT_M(IPC_WCASE)
 #endif
         default: return hipErrorInvalidValue;
     }

@@ -1,12 +1,11 @@
 // Lazy steepest-descent wave kernels of the SE(2) cell solver (se2_wave_kernel.hpp): the instantiations of
 // se2_wave_kernel_lz, which form b^T H b, alpha and |h_sd| only in the iterations whose trial loop reads them (LAZY_SD of
 // se2_wave_solve) and otherwise are the kernel the default policy names for that M: kept trial at M = 5, 7, 9 (kwM),
-// re-sweep at M = 11, 13 (wM).  No policy token: engine.hip serves those bins with these kernels (IPC_SE2_LAZY_SD).
+// re-sweep at M = 11, 13 (wM).  No policy token: the plan serves those bins with these kernels (IPC_SE2_LAZY_SD, cell_plan.hpp).
 #include "se2_wave_kernel.hpp"
 
 namespace ipc {
-hipError_t launch_se2_wave_lz(int nl, int M, int n, hipStream_t st, const Se2View& P, const int2* cells, SolveParams prm,
-                              CellOut out, unsigned* counter, int n_cu)
+IPC_CELL_LAUNCHER(launch_se2_wave_lz, Se2View)
 {
 #define IPC_WCASE(MM)                                                                                                  \
     case MM:                                                                                                           \
@@ -16,11 +15,7 @@ hipError_t launch_se2_wave_lz(int nl, int M, int n, hipStream_t st, const Se2Vie
 #ifdef IPC_WAVE_LZ_ONLY_M                              // (tools/isa_loop_mix.py: one instantiation, seconds to compile)
         IPC_WCASE(IPC_WAVE_LZ_ONLY_M)
 #else
-        IPC_WCASE(5)
-        IPC_WCASE(7)
-        IPC_WCASE(9)
-        IPC_WCASE(11)
-        IPC_WCASE(13)
+        IPC_SE2_WAVE_LZ_M(IPC_WCASE)
 #endif
         default: return hipErrorInvalidValue;
     }

@@ -1,5 +1,7 @@
 // Block kernels of the SE(3) cell solver (se3_cell.hpp): one workgroup per cell.
 #include "cell_kernels.hpp"
+#include "se2_cell.hpp"                              // SolveParams
+#include "se3_cell.hpp"
 
 using namespace ipc;
 
@@ -31,33 +33,15 @@ __global__ __launch_bounds__(64 * W) void se3_cells_kernel(Se3View P, const int2
 }
 
 template <int NL>
-static hipError_t launch_se3(int variant, int n, hipStream_t st, const Se3View& P, const int2* cells,
+static hipError_t launch_se3(int W, int M, int n, hipStream_t st, const Se3View& P, const int2* cells,
                              SolveParams prm, CellOut out)
 {
-#define IPC_CASE3(idx, WW, MM)                                                                    \
-    case idx:                                                                                     \
+#define IPC_CASE3(WW, MM)                                                                         \
+    case cell_wm(WW, MM):                                                                         \
         hipLaunchKernelGGL((se3_cells_kernel<WW, MM, NL>), dim3(n), dim3(64 * WW), 0, st, P, cells, n, prm, out); \
         break;
-    switch (variant) {
-        IPC_CASE3(0, 1, 1)
-        IPC_CASE3(1, 2, 1)
-        IPC_CASE3(2, 4, 1)
-        IPC_CASE3(3, 8, 1)
-        IPC_CASE3(4, 16, 1)
-        IPC_CASE3(5, 16, 2)
-        IPC_CASE3(6, 16, 4)
-        IPC_CASE3(7, 4, 2)
-        IPC_CASE3(8, 4, 4)
-        IPC_CASE3(9, 8, 2)
-        IPC_CASE3(10, 8, 4)
-        IPC_CASE3(11, 4, 8)
-        IPC_CASE3(12, 8, 5)
-        IPC_CASE3(13, 1, 2)
-        IPC_CASE3(14, 2, 2)
-        IPC_CASE3(15, 1, 4)
-        IPC_CASE3(16, 2, 4)
-        IPC_CASE3(17, 1, 3)
-        IPC_CASE3(18, 2, 3)
+    switch (cell_wm(W, M)) {
+        IPC_SE3_BLOCK_WM(IPC_CASE3)
         default: return hipErrorInvalidValue;
     }
 #undef IPC_CASE3
@@ -66,9 +50,8 @@ static hipError_t launch_se3(int variant, int n, hipStream_t st, const Se3View& 
 
 
 namespace ipc {
-hipError_t launch_se3_block(int nl, int variant, int n, hipStream_t st, const Se3View& P, const int2* cells,
-                            SolveParams prm, CellOut out)
+IPC_CELL_LAUNCHER(launch_se3_block, Se3View)
 {
-    return nl == 1 ? launch_se3<1>(variant, n, st, P, cells, prm, out) : launch_se3<2>(variant, n, st, P, cells, prm, out);
+    return nl == 1 ? launch_se3<1>(W, M, n, st, P, cells, prm, out) : launch_se3<2>(W, M, n, st, P, cells, prm, out);
 }
 }  // namespace ipc

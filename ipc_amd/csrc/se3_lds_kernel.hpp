@@ -5,6 +5,7 @@
 #include <algorithm>
 
 #include "cell_kernels.hpp"
+#include "se2_cell.hpp"                              // SolveParams
 #include "se3_lds_cell.hpp"
 
 namespace ipc {

@@ -91,12 +91,13 @@ def _latency_bins_in_play(dim=3):
     """Bins whose kernel variant depends on the NUMBER of cells in the launch (the latency variants of thin bins), from the
     engine's default policies: [(shortest chain, longest chain)] of each such bin.  A cell of such a bin may be solved by another
     kernel in an online update (few cells) than in the batch step; every other cell's kernel depends on its bin alone.
-    launch_slot takes the latency variant of a bin from the plan for either dimension, so SE2 is checked too: the plan gives a
-    bin a latency variant in one place only, and that place is reached for SE3 alone (there is no SE2 latency policy)."""
+    choose_kernel takes the latency variant of a bin from the plan for either dimension, so SE2 is checked too: the plan
+    (make_plan, cell_plan.hpp) gives a bin a latency variant in one place only, and that place is reached for SE3 alone (there
+    is no SE2 latency policy)."""
     assert not os.environ.get("IPC_SE3_POLICY") and not os.environ.get("IPC_SE3_LATENCY_POLICY") and not os.environ.get("IPC_SE2_POLICY")
-    src = open(os.path.join(ROOT, "ipc_amd", "csrc", "engine.hip")).read()
+    src = open(os.path.join(ROOT, "ipc_amd", "csrc", "cell_plan.hpp")).read()
     if dim == 2:
-        sets = [m.start() for m in re.finditer(r"latency_variant\[b\] = (?!-1;)", src)]
+        sets = [m.start() for m in re.finditer(r"latency\[b\] = (?!nullptr;)", src)]
         guard = src.index("if (dim == 3) {")
         assert len(sets) == 1 and guard < sets[0] < src.index("return true;", guard)
         assert "SE2_LATENCY_POLICY" not in src

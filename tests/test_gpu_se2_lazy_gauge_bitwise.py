@@ -4,7 +4,7 @@ use (PARK_GAUGE of se2_wave_solve), and the engine serves the bins of kw9 and kp
 same bits as kw9 and kp9, cell by cell.
 
 Every case builds the engine in this process under IPC_SE2_LAZY_SD=0 (every policy token launches the kernel it names) and
-under =1 (the compiled-in list, kLazySdWaveM / kLazySdPairM of engine.hip) and compares EVERY solved cell -- packed matrix,
+under =1 (the compiled-in list, kLazySdWaveM / kLazySdPairM of cell_plan.hpp) and compares EVERY solved cell -- packed matrix,
 accepted set, max_chi2, chi2_total, iterations, tries, flags, evals -- with array_equal on bit patterns.  Never =2: a kernel
 that is not listed is an error here, the launch counter under =1 must be above zero.
 
@@ -57,8 +57,8 @@ def case_graph(case):
 
 
 def compiled_in():
-    """Tags of the lazy kernels the engine substitutes under IPC_SE2_LAZY_SD=1 (kLazySdWaveM / kLazySdPairM, engine.hip)."""
-    src = open(os.path.join(ROOT, "ipc_amd", "csrc", "engine.hip")).read()
+    """Tags of the lazy kernels the engine substitutes under IPC_SE2_LAZY_SD=1 (kLazySdWaveM / kLazySdPairM, cell_plan.hpp)."""
+    src = open(os.path.join(ROOT, "ipc_amd", "csrc", "cell_plan.hpp")).read()
     tags = set()
     for name, pre in (("kLazySdWaveM", "lw"), ("kLazySdPairM", "lp")):
         m = re.search(r"static const int %s\[\] = \{([^}]*)\}" % name, src)

@@ -5,7 +5,7 @@ A lazy kernel forms b^T H b, alpha and |h_sd| only in the iterations whose trial
 Gauss-Newton, or a Gauss-Newton trial was rejected and the loop goes on), through the same expressions and the same
 reduction order as phases B1 / B2 of the other kernels.  IPC_SE2_LAZY_SD=0 makes every policy token launch the kernel it
 names; =1 (the default) serves those of kw5 kw7 kw9 w11 w13 kp7 kp9 p11 by their lazy forms that the engine's compiled-in
-list names (kLazySdWaveM / kLazySdPairM, engine.hip: the kernels through the static and the measured gate); =2 serves all
+list names (kLazySdWaveM / kLazySdPairM, cell_plan.hpp: the kernels through the static and the measured gate); =2 serves all
 eight, listed or not, so that a kernel outside the list is held to the same bits.  All in the one library, so every case
 builds the engine in this process under =0, under =1 and, where =1 leaves a kernel of the case out, under =2, and compares
 EVERY solved cell -- packed matrix, accepted set, max_chi2,
@@ -72,8 +72,8 @@ def case_graph(case):
 
 
 def compiled_in():
-    """Tags of the lazy kernels the engine substitutes under IPC_SE2_LAZY_SD=1 (kLazySdWaveM / kLazySdPairM, engine.hip)."""
-    src = open(os.path.join(ROOT, "ipc_amd", "csrc", "engine.hip")).read()
+    """Tags of the lazy kernels the engine substitutes under IPC_SE2_LAZY_SD=1 (kLazySdWaveM / kLazySdPairM, cell_plan.hpp)."""
+    src = open(os.path.join(ROOT, "ipc_amd", "csrc", "cell_plan.hpp")).read()
     tags = set()
     for name, pre in (("kLazySdWaveM", "lw"), ("kLazySdPairM", "lp")):
         m = re.search(r"static const int %s\[\] = \{([^}]*)\}" % name, src)

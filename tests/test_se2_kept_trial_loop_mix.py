@@ -9,7 +9,7 @@ NL / staged combination:
     * fewer FP64 instructions in the dog-leg loop body -- and the same number fewer in all four combinations, a multiple
       of M: one commit-sweep slot (both its small-rotation and its full-sincos branch) times M, nothing left of it
       (68 per slot where the commit also re-evaluated the error, M = 5 and 7; 51 per slot at M = 9 and 11).
-The default policy (kDefaultPolicy, engine.hip) names a kept-trial kernel only where the table shows all four of its
+The default policy (kDefaultPolicy, cell_plan.hpp) names a kept-trial kernel only where the table shows all four of its
 combinations through this gate.  The translation units of the old kernels must emit the old kernels only, and the new
 units the new kernels only; tests/test_se2_loop_mix.py and tests/test_se2_keep_errors_loop_mix.py hold the old kernels'
 loop bodies to their own tables."""
@@ -43,7 +43,7 @@ def gate(kept, old):
 
 
 def default_policy():
-    src = open(os.path.join(ROOT, "ipc_amd", "csrc", "engine.hip")).read()
+    src = open(os.path.join(ROOT, "ipc_amd", "csrc", "cell_plan.hpp")).read()
     return re.search(r'kDefaultPolicy = "([^"]+)"', src).group(1).split(",")
 
 

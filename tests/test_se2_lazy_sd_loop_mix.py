@@ -11,7 +11,7 @@ p11 -- IN THE SAME BUILD, for every NL / staged combination:
     * fewer VALU instructions in the dog-leg loop body outside the sd_terms() block.
 The static FP64 count of the whole body is no gate: the block moves, it does not vanish.
 
-The engine substitutes a lazy kernel (kLazySdWaveM / kLazySdPairM, engine.hip) only where the table shows all four of
+The engine substitutes a lazy kernel (kLazySdWaveM / kLazySdPairM, cell_plan.hpp) only where the table shows all four of
 its combinations through this gate."""
 import os
 import re
@@ -48,8 +48,8 @@ def gate(lazy, old):
 
 
 def compiled_in():
-    """Tags of the kernels the engine substitutes (kLazySdWaveM / kLazySdPairM of engine.hip)."""
-    src = open(os.path.join(ROOT, "ipc_amd", "csrc", "engine.hip")).read()
+    """Tags of the kernels the engine substitutes (kLazySdWaveM / kLazySdPairM of cell_plan.hpp)."""
+    src = open(os.path.join(ROOT, "ipc_amd", "csrc", "cell_plan.hpp")).read()
     tags = []
     for name, pre in (("kLazySdWaveM", "lw"), ("kLazySdPairM", "lp")):
         m = re.search(r"static const int %s\[\] = \{([^}]*)\}" % name, src)
