@@ -426,6 +426,8 @@ int ipc_run_exact(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accepted_out, ui
 #include "ipc_amd_lazy_sd.h"
 /* ... and the sets of every run of a Monte-Carlo batch, likewise. */
 #include "ipc_amd_batch_exact.h"
+/* ... and the census of the maximum consistent sets -- count, core and support, likewise. */
+#include "ipc_amd_census.h"
 
 /* Diagnostics of the last ipc_solve_rows(), ipc_run_online(), ipc_run_sweep() or ipc_run_batch(): number of solved cells, and their records. */
 int ipc_cell_count(ipc_engine_t* h, int* n_cells);

@@ -46,6 +46,8 @@ SYMBOLS_ONLINE_EXACT = ["ipc_set_max_exact_resume", "ipc_run_online_exact", "ipc
 SYMBOLS_LAZY_SD = ["ipc_se2_lazy_sd_launches"]
 # every symbol include/ipc_amd_batch_exact.h declares (checked by tests/test_batch_exact_cpu.py)
 SYMBOLS_BATCH_EXACT = ["ipc_set_max_batch_exact", "ipc_run_batch_exact"]
+# every symbol include/ipc_amd_census.h declares (checked by tests/test_census_cpu.py)
+SYMBOLS_CENSUS = ["ipc_set_max_census", "ipc_run_census"]
 
 
 class Params(C.Structure):
@@ -112,6 +114,12 @@ class BatchExactReport(C.Structure):
                 ("set_launches", C.c_int), ("set_host_waits", C.c_int)]
 
 
+class CensusReport(C.Structure):
+    _fields_ = [("live", C.c_int), ("size", C.c_int), ("exact_proven", C.c_int), ("proven", C.c_int), ("count", C.c_longlong),
+                ("core_size", C.c_int), ("support_size", C.c_int), ("subproblems", C.c_int), ("capped", C.c_int),
+                ("steps", C.c_longlong)]
+
+
 CELL_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("lo", "<i4"), ("hi", "<i4"), ("max_chi2", "<f8"),
                        ("chi2_total", "<f8"), ("iterations", "<i4"), ("tries", "<i4"), ("flags", "<i4"),
                        ("evals", "<i4")])
@@ -173,6 +181,9 @@ def load():
     if hasattr(lib, "ipc_run_batch_exact"):            # (an A/B library of an older build lacks them)
         lib.ipc_set_max_batch_exact.argtypes = [vp, ip, vp, vp, vp, vp, vp, vp, vp, C.POINTER(BatchExactReport), vp]
         lib.ipc_run_batch_exact.argtypes = [vp, ip, vp, vp, vp, vp, vp, vp, C.POINTER(BatchReport), vp, C.POINTER(BatchExactReport)]
+    if hasattr(lib, "ipc_run_census"):                 # (an A/B library of an older build lacks them)
+        lib.ipc_set_max_census.argtypes = [vp, vp, vp, vp, vp, C.POINTER(ExactReport), C.POINTER(CensusReport), vp]
+        lib.ipc_run_census.argtypes = [vp, vp, vp, vp, vp, C.POINTER(ExactReport), C.POINTER(CensusReport)]
     lib.ipc_run_sharded.argtypes =[C.POINTER(vp), ip, vp, vp]
     lib.ipc_run_set_only.argtypes = [vp, vp, C.POINTER(ip)]
     lib.ipc_cell_count.argtypes = [vp, C.POINTER(ip)]

@@ -277,6 +277,22 @@ class IPC:
         report = {k: getattr(r, k) for k, _ in capi.ExactReport._fields_}
         return (bits, acc, ms, report) if want_bits else (acc, ms, report)
 
+    # ---- census of the maximum consistent sets: how many there are, what they share, what any of them holds ----
+    def run_census(self, want_bits=False):
+        """ipc_run_census: run_exact()'s matrix and exact set, then the census of the maximum consistent sets.  Returns (accepted
+        [N] uint8, core [N] uint8, support [N] uint8, exact report dict, census report dict), with want_bits the bits [N, words]
+        uint64 in front; bits, accepted and the exact report are those of run_exact().  census["proven"] = 1: there are
+        census["count"] maximum sets, core marks the candidates in all of them and support those in any; 0: count is a lower
+        bound (0 where the exact stage proved nothing), core is empty and support is the live candidates.
+        getMaxConsensusSet() is left as it was."""
+        acc, core, support = (np.zeros(self.N, dtype=np.uint8) for _ in range(3))
+        bits = np.zeros((self.N, self.words), dtype=np.uint64) if want_bits else None
+        r, c = capi.ExactReport(), capi.CensusReport()
+        capi.check(self.lib.ipc_run_census(self.h, _p(bits) if want_bits else None, _p(acc), _p(core), _p(support), C.byref(r), C.byref(c)))
+        exact = {k: getattr(r, k) for k, _ in capi.ExactReport._fields_}
+        census = {k: getattr(c, k) for k, _ in capi.CensusReport._fields_}
+        return (bits, acc, core, support, exact, census) if want_bits else (acc, core, support, exact, census)
+
     def consistency_matrix(self):
         bits, _ = self.run()
         return unpack_bits(bits, self.N)
@@ -371,6 +387,14 @@ class IPC:
         r = capi.ExactReport()
         capi.check(self.lib.ipc_set_max_exact(self.h, C.c_void_p(d_bits_ptr), C.c_void_p(d_accepted_ptr), C.byref(r), C.c_void_p(stream)))
         return {k: getattr(r, k) for k, _ in capi.ExactReport._fields_}
+
+    def set_max_census(self, d_bits_ptr, d_accepted_ptr, d_core_ptr, d_support_ptr, stream=0):
+        """ipc_set_max_census on device pointers; blocks until the census is over and returns (exact report dict, census report
+        dict)."""
+        r, c = capi.ExactReport(), capi.CensusReport()
+        capi.check(self.lib.ipc_set_max_census(self.h, C.c_void_p(d_bits_ptr), C.c_void_p(d_accepted_ptr), C.c_void_p(d_core_ptr),
+                                               C.c_void_p(d_support_ptr), C.byref(r), C.byref(c), C.c_void_p(stream)))
+        return ({k: getattr(r, k) for k, _ in capi.ExactReport._fields_}, {k: getattr(c, k) for k, _ in capi.CensusReport._fields_})
 
     def set_max_batch_exact(self, run_n, order, d_bits_ptr, d_accepted_ptr, d_multistart_ptr=0, d_greedy_ptr=0, stream=0):
         """ipc_set_max_batch_exact on device pointers: run_n [R] and order (the runs' processing orders back to back) are host

@@ -731,6 +731,13 @@ struct ipc_engine {
         unsigned* steps() const { return (unsigned*)vec.part(d_vec, 2); }
     } ex;
     unsigned ex_step_cap = 1u << 20;                   // IPC_EXACT_STEP_CAP: steps after which a subproblem gives up
+    // Census of the maximum consistent sets (ipc_set_max_census), behind the exact stage and over its P: the
+    // [2][128] accumulator (core, support; census_kernels.hpp), the info words and ipc_run_census's core and support bytes.
+    // Flags, counts, steps and stacks are those of `ex`.
+    struct CensusScratch {
+        DevBuf<unsigned long long> d_acc; DevBuf<int> d_info;
+        DevBuf<unsigned char> d_out; ScratchCap out;   // d_out [2][out]
+    } cs;
     // The sets of a batch (ipc_set_max_batch_exact, ipc_run_batch_exact), for a chunk of runs: descriptors, open
     // runs and info words per run (batch_exact_kernels.hpp), the compact matrices (words), eight int vectors per run (order,
     // live, pos, sz, flag, size, steps, the greedy's live list), ipc_run_batch_exact's multi-start and accepted bytes, the
@@ -1600,6 +1607,7 @@ __device__ __forceinline__ int slot_of_cell(const unsigned* slot_off, int nslots
 #include "batch_kernels.hpp"
 #include "multistart_kernels.hpp"
 #include "exact_kernels.hpp"
+#include "census_kernels.hpp"
 #include "exact_resume_kernels.hpp"
 #include "batch_exact_kernels.hpp"
 // Failed cells -> list (host-driven Levenberg retry, rare); borderline cells -> the compact list of their slot (lit_cells /
@@ -2326,6 +2334,90 @@ extern "C" int ipc_run_exact(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accep
     if (int rc = run_matrix(h)) return rc;
     if (int rc = set_max_exact(h, h->run.d_bits, (h->N + 63) / 64, h->ms.d_acc, report, h->own_stream, multistart_out)) return rc;
     return run_copy_out(h, bits_out, accepted_out, h->ms.d_acc);
+}
+
+// ------------------------------------------------------------------------------------------
+// census of the maximum consistent sets: count, core and support, behind the exact stage (census_kernels.hpp)
+// ------------------------------------------------------------------------------------------
+// set_max_exact as it is, then -- where it proved omega and somebody is live -- the search over every root with the bound frozen
+// at omega - 1, and the pick, which also writes the trivial bounds where no search ran.  One host wait behind the exact stage's.
+static int set_max_census(ipc_engine* h, const uint64_t* d_bits, int stride, uint8_t* d_accepted, uint8_t* d_core, uint8_t* d_support,
+                          ipc_exact_report_t* exact_report, ipc_census_report_t* report, hipStream_t st)
+{
+    const int N = h->N, words = (N + 63) / 64;
+    ipc_exact_report_t ex{};
+    if (int rc = set_max_exact(h, d_bits, stride, d_accepted, &ex, st, nullptr)) return rc;
+    if (!h->cs.d_acc) HIPCHK(h->cs.d_acc.alloc(2 * (size_t)((kExLimitN + 63) / 64)));
+    if (!h->cs.d_info) HIPCHK(h->cs.d_info.alloc(kCsInfo));
+    const int n = ex.live, omega = ex.size;
+    const bool search = ex.proven && n > 0;
+    const unsigned long long* P = h->ms.d_P;
+    const int* ms_info = h->ms.d_info;
+    unsigned long long* acc = h->cs.d_acc;
+    int* info = h->cs.d_info;
+    int* flag = h->ex.flag(); int* count = h->ex.sizes(); unsigned* steps = h->ex.steps();
+    if (search) {
+        ExactSearch S;
+        if (int rc = exact_workspace_for(h, n, 64 * (words <= 64 ? 1 : 2) + (n + 3) / 4 + 1, omega, 0, "ipc_set_max_census", "live candidates", S))
+            return rc;
+        HIPCHK(hipMemsetAsync(acc, 0xff, sizeof(unsigned long long) * words, st));
+        HIPCHK(hipMemsetAsync(acc + words, 0, sizeof(unsigned long long) * words, st));
+        HIPCHK(hipMemsetAsync(info, 0, sizeof(int), st));
+        IPC_EX_LAUNCH(k_cs_search, words, S.grid, S.block, st, words, S.levels, S.level_words, S.slice_words, h->ex_step_cap, omega, P, ms_info,
+                      info, (unsigned long long*)h->ex.d_ws, flag, count, steps, acc);
+    }
+    hipLaunchKernelGGL(k_cs_pick, dim3(1), dim3(1024), 0, st, N, words, search ? 1 : 0, (const int*)h->ms.live(), ms_info, (const int*)flag,
+                       (const int*)count, (const unsigned*)steps, (const unsigned long long*)acc, info, d_core, d_support);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    int cs[kCsInfo];
+    HIPCHK(hipMemcpy(cs, info, sizeof(cs), hipMemcpyDeviceToHost));
+    ipc_census_report_t rep{};
+    rep.live = n; rep.size = ex.size; rep.exact_proven = ex.proven;
+    rep.core_size = cs[7]; rep.support_size = cs[8];
+    if (search) {
+        rep.subproblems = cs[1]; rep.capped = cs[2];
+        rep.steps = exact_steps(cs[3], cs[4]);
+        rep.count = exact_steps(cs[5], cs[6]);
+        rep.proven = rep.capped == 0 ? 1 : 0;
+    } else if (ex.proven) {                              // n = 0: the empty set is the one maximum set
+        rep.proven = 1; rep.count = 1;
+    }
+    if (exact_report) *exact_report = ex;
+    if (report) *report = rep;
+    return IPC_OK;
+}
+
+extern "C" int ipc_set_max_census(ipc_engine_t* h, const uint64_t* d_bits, uint8_t* d_accepted, uint8_t* d_core, uint8_t* d_support,
+                                  ipc_exact_report_t* exact_report, ipc_census_report_t* report, void* stream)
+{
+    if (!h || !d_bits || !d_accepted || !d_core || !d_support) return fail(IPC_ERR_ARG, "ipc_set_max_census: NULL argument");
+    if (h->N <= 0) return fail(IPC_ERR_STATE, "ipc_set_max_census: no candidates set");
+    if (h->N > kExLimitN) return fail(IPC_ERR_LIMIT, "ipc_set_max_census: N=%d exceeds %d candidates", h->N, kExLimitN);
+    HIPCHK(hipSetDevice(h->device));
+    return set_max_census(h, d_bits, (h->N + 63) / 64, d_accepted, d_core, d_support, exact_report, report,
+                          stream ? (hipStream_t)stream : h->own_stream);
+}
+
+extern "C" int ipc_run_census(ipc_engine_t* h, uint64_t* bits_out, uint8_t* accepted_out, uint8_t* core_out, uint8_t* support_out,
+                              ipc_exact_report_t* exact_report, ipc_census_report_t* report)
+{
+    if (!h) return fail(IPC_ERR_ARG, "ipc_run_census: NULL handle");
+    if (h->N <= 0) return fail(IPC_ERR_STATE, "ipc_run_census: no candidates set");
+    if (h->N > kExLimitN) return fail(IPC_ERR_LIMIT, "ipc_run_census: N=%d exceeds %d candidates", h->N, kExLimitN);
+    HIPCHK(hipSetDevice(h->device));
+    const size_t N = (size_t)h->N;
+    if (int rc = ensure_run_scratch(h)) return rc;
+    if (int rc = ensure_multistart_scratch(h, h->N, run_words(h))) return rc;
+    HIPCHK(h->cs.out.grow(N, sized(h->cs.d_out, 2 * N)));
+    unsigned char* d_core = h->cs.out.part(h->cs.d_out, 0);
+    unsigned char* d_support = h->cs.out.part(h->cs.d_out, 1);
+    if (int rc = run_matrix(h)) return rc;
+    if (int rc = set_max_census(h, h->run.d_bits, (h->N + 63) / 64, h->ms.d_acc, d_core, d_support, exact_report, report, h->own_stream)) return rc;
+    if (int rc = run_copy_out(h, bits_out, accepted_out, h->ms.d_acc)) return rc;
+    if (core_out) HIPCHK(hipMemcpy(core_out, d_core, N, hipMemcpyDeviceToHost));
+    if (support_out) HIPCHK(hipMemcpy(support_out, d_support, N, hipMemcpyDeviceToHost));
+    return IPC_OK;
 }
 
 // ------------------------------------------------------------------------------------------

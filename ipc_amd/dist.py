@@ -68,6 +68,11 @@ class EngineBackend:
         """The exact set or its bracket (ipc_set_max_exact): accepted [N] uint8; blocks the host, returns the report dict."""
         return self.e.set_max_exact(bits.data_ptr(), accepted.data_ptr(), self._stream())
 
+    def set_max_census(self, bits, accepted, core, support):
+        """The exact set and the census of the maximum sets (ipc_set_max_census): accepted, core and support [N] uint8; blocks
+        the host, returns (exact report dict, census report dict)."""
+        return self.e.set_max_census(bits.data_ptr(), accepted.data_ptr(), core.data_ptr(), support.data_ptr(), self._stream())
+
     def set_max_batch_exact(self, run_n, order, bits, accepted, multistart=None, greedy=None):
         """The sets of a batch of matrices (ipc_set_max_batch_exact): bits holds the matrices back to back, accepted, multistart
         and greedy [sum N_r] uint8 with the offsets of `order` (host, the runs' orders back to back); blocks the host, returns
